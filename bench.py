@@ -17,6 +17,13 @@ equal ``--gpus`` or the run fails (exit 2) instead of measuring a different worl
 A timed step = synthetic batch generation + corruption, forward, loss,
 backward, bucketed RCCL all-reduce (N>1) and the fused Adam update.
 Rank 0 prints ONE JSON line; the time is the max over ranks.
+
+A plain run does only that: set up, ``--warmup`` steps, ``--steps`` timed steps (``ms_per_step`` is one of
+them), the result line.  ``--dump-outputs DIR`` also writes what the last timed step left behind (loss,
+per-head losses, a seeded sample of the updated parameters) as ``DIR/<name>.npy``; the same arguments give
+the same inputs, so two builds can be compared array by array.  ``--full`` is the switch for measurements
+beyond the headline figure (none in this script today: other precisions, lengths and modes are separate
+invocations).
 """
 from __future__ import annotations
 
@@ -73,6 +80,13 @@ def parse():
                          "step; DP=N then equals the single-process batch-N*b step)")
     ap.add_argument("--semantics", default="reference", choices=["reference", "paper"],
                     help="paper: published attention/LN/softmax (per-position LayerNorm, softmax over positions)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, per-head losses, "
+                         "a fixed seeded sample of the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure; a plain run sets up, warms up, "
+                         "times --steps steps and prints the result line, which is all this benchmark measures "
+                         "in one process, so the option adds nothing yet")
     return ap.parse_args()
 
 
@@ -176,6 +190,9 @@ def main():
 
     dt, loss = _timed(one, a, info, dev)
     final_loss = float(loss.item())
+    if a.dump_outputs and info.is_main:
+        l_local, l_global = step.last_parts
+        _dump_outputs(a.dump_outputs, {"loss": loss, "loss_local": l_local, "loss_global": l_global}, opt.arena)
     n = info.world_size
     value = n * B * a.steps / dt
     if info.is_main:
@@ -250,6 +267,27 @@ def _timed(one, a, info, dev):
     return pdist.all_reduce_max(time.perf_counter() - t0, dev), loss
 
 
+DUMP_SAMPLE = 8 << 20   # parameter elements written by --dump-outputs (32 MiB as float32)
+
+
+def _dump_outputs(path: str, scalars, arena) -> None:
+    """What a caller of the timed step holds after the last one: the returned loss (and per-head losses)
+    and the updated parameters (the flat arena; the gradient arena is the step's scratch, rewritten by
+    the next one).  An arena larger than DUMP_SAMPLE elements is written as the same seeded sample of
+    positions in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in scalars.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().double().cpu().numpy())
+    n = arena.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240607).choice(n, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(arena.data.device)
+    v = arena.data.detach() if idx is None else arena.data.detach()[idx]
+    np.save(os.path.join(path, "params.npy"), v.float().cpu().numpy())
+
+
 def finetune_bench(a, info, encoder, L, B, mcfg):
     """BASELINE cfg 5: the fine-tune step of a frozen pretrained encoder (random-init here) with a
     per-residue secondary-structure head (reference train_step contract, utils.py:110-168: CE over
@@ -280,6 +318,8 @@ def finetune_bench(a, info, encoder, L, B, mcfg):
         return loss.detach()
 
     dt, loss = _timed(one, a, info, dev)
+    if a.dump_outputs and info.is_main:
+        _dump_outputs(a.dump_outputs, {"loss": loss}, opt.arena)
     n = info.world_size
     value = n * B * a.steps / dt
     if info.is_main:

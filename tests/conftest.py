@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE_DIR = "/root/reference/ProteinBERT"
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
 
 def pytest_configure(config):
@@ -26,16 +26,15 @@ def pytest_collection_modifyitems(config, items):
 
 
 @pytest.fixture(scope="session")
-def reference_modules():
-    """The reference model file imports with torch alone."""
-    if not os.path.exists(os.path.join(REFERENCE_DIR, "modules.py")):
-        pytest.skip("reference not mounted")
-    sys.path.insert(0, REFERENCE_DIR)
-    try:
-        import modules  # type: ignore
-    finally:
-        sys.path.remove(REFERENCE_DIR)
-    return modules
+def reference_golden():
+    """What the reference ``modules.py`` computed (fp32, CPU) on the parity tests' configuration, recorded
+    by tools/make_reference_golden.py: a read-only dict of torch tensors, plus ``param_names``, the
+    reference's ``named_parameters()`` order."""
+    import numpy as np
+    import torch
+    with np.load(os.path.join(GOLDEN_DIR, "reference_parity.npz")) as z:
+        rec = {k: (list(z[k]) if k == "param_names" else torch.from_numpy(z[k])) for k in z.files}
+    return rec
 
 
 def _exported_launchers():

@@ -66,6 +66,43 @@ def test_bench_rejects_world_size_mismatch():
     assert not _json_lines(r.stdout)
 
 
+def test_bench_dump_outputs_and_full_cpu(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's results as float32/float64 ``.npy`` files (at most
+    64 MB), the same arguments give the same inputs and so the same outputs, ``--steps`` sets the number of
+    timed steps (two steps leave other parameters than three), and ``--full`` keeps the result line."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+
+    def run(name, steps, *extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--batch", "2", "--seq-len", "32", "--dump-outputs", str(tmp_path / name), *extra]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        arrays = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        return lines[0], arrays
+
+    d1, a1 = run("a", 2)
+    d2, a2 = run("b", 2, "--full")
+    d3, a3 = run("c", 3)
+    assert KEYS <= set(d1) and KEYS <= set(d2)
+    assert d1["steps"] == d2["steps"] == 2 and d3["steps"] == 3
+    assert {k: d1[k] for k in ("metric", "unit", "higher_is_better", "dtype")} == \
+        {k: d2[k] for k in ("metric", "unit", "higher_is_better", "dtype")}
+    assert abs(d1["value"] - 2 * 1000.0 / d1["ms_per_step"]) / d1["value"] < 0.02
+    assert set(a1) == {"loss", "loss_local", "loss_global", "params"}
+    assert sum(v.nbytes for v in a1.values()) <= 64 * 2 ** 20
+    for k, v in a1.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+        np.testing.assert_allclose(a2[k], v, rtol=1e-6, atol=1e-9, err_msg=k)
+    assert abs(float(a1["loss"]) - d1["final_loss"]) < 1e-5
+    assert abs(float(a1["loss_local"]) + float(a1["loss_global"]) - float(a1["loss"])) < 1e-5
+    assert a1["params"].ndim == 1 and a1["params"].size > 1000
+    assert np.abs(a3["params"] - a1["params"]).max() > 0
+
+
 def test_default_presets_size_batches_per_length():
     """Without --preset the bench takes the BASELINE preset of the mode / sequence length: ~1M tokens per
     GPU and step (cfg 2: 2048 x 512, cfg 3: 1024 x 1024, cfg 4: 256 x 4096, cfg 5 fine-tune: 2048 x 512)."""

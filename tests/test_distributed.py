@@ -180,7 +180,10 @@ def test_dp_overlapped_optimizer_catches_summed_overflow(tmp_path, where):
 def _pretrain_worker(rank, world, port, save, zero=False):
     _env(rank, world, port)
     torch.set_num_threads(1)
+    from proteinbert_pytorch_replication_amd.parallel import dist as pdist
     from proteinbert_pytorch_replication_amd.train.pretrain import pretrain
+    # a CPU job, also on a machine with fewer GPUs than ranks: pretrain() takes the group opened here
+    pdist.init_distributed(device="cpu")
     torch.manual_seed(0)
     m = ProteinBERT(backend="torch", **CFG)
     gen = SyntheticUniRefGO(CFG["sequences_length"], CFG["num_annotations"], 4, "cpu", seed=rank, use_kernel=False)
@@ -273,9 +276,13 @@ def test_rccl_node_defaults_respect_environment(monkeypatch):
     multi-node jobs, and not at all with PBX_RCCL_DEFAULTS=0."""
     from proteinbert_pytorch_replication_amd.parallel import dist as pdist
     for k in pdist.RCCL_NODE_DEFAULTS:
-        monkeypatch.delenv(k, raising=False)
+        monkeypatch.setenv(k, "")               # so that teardown also removes what the call under test sets
+        monkeypatch.delenv(k)
     monkeypatch.setenv("NCCL_MIN_NCHANNELS", "32")
     monkeypatch.setenv("LOCAL_WORLD_SIZE", "8")
+    # the case under test is a process that has not started HSA yet (an earlier GPU test of the same
+    # session may have): HSA_* defaults are left alone once the runtime has read them
+    monkeypatch.setattr(torch.cuda, "is_initialized", lambda: False)
     applied = pdist.rccl_node_defaults(8)
     assert os.environ["NCCL_MIN_NCHANNELS"] == "32" and "NCCL_MIN_NCHANNELS" not in applied
     assert os.environ["HSA_NO_SCRATCH_RECLAIM"] == "1"

@@ -98,20 +98,29 @@ def test_pretrain_checkpoint_and_resume(tmp_path):
     assert finals
 
 
-def test_checkpoint_loads_into_reference(reference_modules, tmp_path):
+def test_checkpoint_loads_into_reference(reference_golden, tmp_path):
+    """The reference model is stood in for by its recorded state dict and ``named_parameters()`` order
+    (tests/golden/reference_parity.npz): a strict ``load_state_dict`` needs exactly its keys and shapes,
+    and its Adam takes our optimizer state only if the parameters line up one to one."""
+    ref_state = {k[len("state/"):]: v for k, v in reference_golden.items() if k.startswith("state/")}
     m = _model()
     gen = SyntheticUniRefGO(CFG["sequences_length"], CFG["num_annotations"], 2, "cpu", seed=3, use_kernel=False)
     pretrain(m, gen, torch.optim.Adam(m.parameters(), lr=1e-3), max_batch_iterations=2,
              save_path=str(tmp_path), nb_iterations_checkpoint=1, warmup_duration=1, final_save=False)
     blob = load_checkpoint(str(tmp_path / "proteinbert_pretraining_checkpoint_1.pt"))
-    ref = reference_modules.ProteinBERT(device="cpu", **CFG)
-    ref.load_state_dict(blob["model_state_dict"], strict=True)
-    ref_opt = torch.optim.Adam(ref.parameters(), lr=1e-3)
+    ours = blob["model_state_dict"]
+    assert list(ours.keys()) == list(ref_state.keys())
+    for k, v in ref_state.items():
+        assert ours[k].shape == v.shape and ours[k].dtype == v.dtype, k
+    ref_params = [torch.nn.Parameter(torch.empty_like(ref_state[n])) for n in reference_golden["param_names"]]
+    ref_opt = torch.optim.Adam(ref_params, lr=1e-3)
     ref_opt.load_state_dict(blob["optimizer_state_dict"])
+    for p, st in zip(ref_params, ref_opt.state_dict()["state"].values()):
+        assert st["exp_avg"].shape == p.shape
     # and a reference-produced checkpoint loads into ours (heads re-drawn)
     m2 = _model(seed=5)
-    load_reference_checkpoint(m2, {"model_state_dict": ref.state_dict()})
-    torch.testing.assert_close(m2.state_dict()["local_embedding.weight"], ref.state_dict()["local_embedding.weight"])
+    load_reference_checkpoint(m2, {"model_state_dict": ref_state})
+    torch.testing.assert_close(m2.state_dict()["local_embedding.weight"], ref_state["local_embedding.weight"])
 
 
 def test_pretrain_profile_window_writes_trace(tmp_path):
