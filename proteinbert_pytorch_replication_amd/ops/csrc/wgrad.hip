@@ -12,10 +12,14 @@
 // the 256 AGPRs: hipcc shuffles accumulators through VGPR copies around every MFMA.)
 //
 // Staging is asynchronous global->LDS DMA (global_load_lds_dwordx4, 1 KiB per wave instruction,
-// lane-linear destination) into two LDS buffers: the loads of tile t+1 are issued before the MFMAs
-// of tile t, and one barrier per tile retires them.  The x tile keeps the swz256 image of the other
-// kernels by permuting the per-lane SOURCE chunk (the destination of a DMA cannot be permuted);
-// rows outside the sequence (conv zero padding) read a 16-byte zero block.
+// lane-linear destination) into two LDS buffers: the loads of tile t+1 are issued one per step inside
+// the first MFMA steps of tile t (the SIMD partner's MFMAs cover their issue cost; nothing but the
+// first fragment reads stands between the tile's barrier and its first MFMA), and one barrier per
+// tile retires them.  A wave's DMA list is fixed for the whole kernel (Stage2 / StageTok below): per
+// tile only a running sample base, the tile's first position and the in-range test change, in 32-bit
+// scalar arithmetic.  The x tile keeps the swz256 image of the other kernels by permuting the
+// per-lane SOURCE chunk (the destination of a DMA cannot be permuted); rows outside the sequence
+// (conv zero padding) read a 16-byte zero block (a v_cndmask on the address, no branch).
 //
 // Partials go to fp32 slabs in tap-major layout [chunk][conv][k][co][ci] (each store instruction
 // covers 2 x 128 contiguous bytes); wgrad2_reduce sums the chunks in fixed order (deterministic)
@@ -49,9 +53,63 @@ __device__ __forceinline__ void glds16(const void* src, unsigned char* lds_base)
                : "memory");
 }
 
-// The tile loop of one wave: NTAP taps k0.. of input-channel tile cig, both 32-co tiles.
-template <int NTAP, int BIAS, typename StageF>   // BIAS: 0 none, 1 / 2: sum co tile 0 / 1
-__device__ __forceinline__ void wgrad_tiles(unsigned char* smem, int buf_bytes, long t0, long t1, StageF& stage,
+// Address of a device global, read once: an opaque copy keeps hipcc from re-loading it through the GOT
+// (a scalar-cache round trip) at every use.
+__device__ __forceinline__ unsigned long opaque_addr(const void* p) {
+  unsigned long a = (unsigned long)p;
+  asm volatile("" : "+s"(a));
+  return a;
+}
+
+constexpr int MAXE2 = 10;   // DMAs per wave per tile: ceil((16 + XR / 4) / 8), XR <= 256 (the LDS limit)
+
+// The DMA list of wave w for one tile of wgrad2: entry e is instruction i = w + 8 e of the tile's
+// 16 + XR / 4 (dealt round-robin to the 8 waves).  Entries 0 and 1 are the wave's dy rows 16 w ..
+// (co sub-tile e: 16 rows x 64 B), entries e >= 2 its x rows 4 w + 32 (e - 2) .. (4 rows x 256 B,
+// swz256 image: the chunk permutation depends on row & 15 = 4 (w & 3) + (lane >> 4) only).  So the
+// per-lane source offsets and rows are fixed, an entry adds a constant, and a tile moves only the
+// uniform part: pos0 and the sample bases (b, t advance as a running pair, no division).
+struct Stage2 {
+  unsigned long dyb, xb;   // byte address of the sample's dy row 0 (+ the co half) / of its x row -halo
+  unsigned long dys, xs;   // bytes per sample
+  unsigned long zero;      // the zero block
+  int pos0, L;             // first position of the tile to stage
+  int n, w;                // DMA instructions per tile; this wave
+  int xsh;                 // x row pos0 + row is real if (unsigned)(pos0 + row + xsh) < xspan
+  unsigned xspan;
+  int rowdy, rowx;         // per lane: row of the entry-0 dy / entry-2 x instruction
+  unsigned dyoff, xoff;    // per lane: byte offset of that row's 16 bytes from the tile's first row
+
+  __device__ __forceinline__ void issue(int e, int nn, unsigned char* buf) const {
+    if (w + 8 * e >= nn) return;               // (uniform)
+    if (e < 2) {
+      const unsigned long a = dyb + (unsigned long)(unsigned)pos0 * 256u + dyoff + e * 64;
+      glds16((const void*)(pos0 + rowdy < L ? a : zero), buf + e * (BM * 64) + w * 1024);
+    } else {
+      const int r0 = pos0 + 32 * (e - 2);
+      const unsigned long a = xb + (unsigned long)(unsigned)r0 * 256u + xoff;
+      glds16((const void*)((unsigned)(r0 + rowx + xsh) < xspan ? a : zero),
+             buf + BM * 128 + (w + 8 * (e - 2)) * 1024);
+    }
+  }
+  __device__ __forceinline__ void all(unsigned char* buf) const {
+#pragma unroll
+    for (int e = 0; e < MAXE2; ++e) issue(e, n, buf);
+  }
+  __device__ __forceinline__ void next() {
+    pos0 += BM;
+    if (pos0 >= L) {
+      pos0 = 0;
+      dyb += dys;
+      xb += xs;
+    }
+  }
+};
+
+// The tile loop of one wave: NTAP taps k0.. of input-channel tile cig, both 32-co tiles, over `nt`
+// tiles starting at the one `sg` points to.
+template <int NTAP, int BIAS>   // BIAS: 0 none, 1 / 2: sum co tile 0 / 1
+__device__ __forceinline__ void wgrad_tiles(unsigned char* smem, int buf_bytes, int nt, Stage2& sg,
                                             f32x16_t (&acc0)[5], f32x16_t (&acc1)[5], float& bsum, int halo,
                                             int d, int k0, int cig, int lane) {
   const int h = lane >> 5, q = tr_q(lane), tc = tr_c(lane);
@@ -64,17 +122,21 @@ __device__ __forceinline__ void wgrad_tiles(unsigned char* smem, int buf_bytes, 
     xoff[j] = BM * 128 + swz256e(rb, cig * 32 + tc);
     xoff4[j] = BM * 128 + swz256e(rb + 4, cig * 32 + tc);
   }
-  if (t0 < t1) stage(t0, smem);
-  for (long tile = t0; tile < t1; ++tile) {
-    unsigned char* cur = smem + ((tile - t0) & 1) * buf_bytes;
-    unsigned char* nxt = smem + (((tile - t0) & 1) ^ 1) * buf_bytes;
+  if (nt > 0) {
+    sg.all(smem);
+    sg.next();
+  }
+  for (int it = 0; it < nt; ++it) {
+    unsigned char* cur = smem + (it & 1) * buf_bytes;
+    unsigned char* nxt = smem + ((it & 1) ^ 1) * buf_bytes;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of `cur` landed
     __syncthreads();                                   // ... every wave's; `nxt` no longer read
-    if (tile + 1 < t1) stage(tile + 1, nxt);
+    const int nn = it + 1 < nt ? sg.n : 0;             // DMAs of the next tile (issued in steps 0..)
     // (K-step kk, tap j) steps s = kk * NTAP + j: the x fragment of step s + 2 (and the dy fragments
     // of the next K-step) are read while the MFMA pair of step s runs -- a 3-slot register ring that
     // keeps two LDS reads in flight ahead of the MFMAs without the VGPRs of a whole K-step
     constexpr int NS = (BM / 16) * NTAP;
+    static_assert(MAXE2 <= NS, "one DMA per step");
     bf16x8 fa0[2], fa1[2], fb[3];
     auto read_a = [&](int kk) {
       const unsigned char* c = cur + kk * 16 * 64;     // dy rows advance 16 x 64 B
@@ -96,6 +158,9 @@ __device__ __forceinline__ void wgrad_tiles(unsigned char* smem, int buf_bytes, 
         read_b(st + 2);
       }
       __builtin_amdgcn_sched_barrier(0);
+      // the next tile's DMA e = st, behind the step's LDS reads: it writes `nxt`, which no wave reads
+      // before the next barrier, and the vmcnt(0) above that barrier retires it
+      if (st < MAXE2) sg.issue(st, nn, nxt);
       if (BIAS != 0 && j == 0) {
         typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
         const u32x4 u = __builtin_bit_cast(u32x4, BIAS == 2 ? fa1[kk & 1] : fa0[kk & 1]);
@@ -106,6 +171,7 @@ __device__ __forceinline__ void wgrad_tiles(unsigned char* smem, int buf_bytes, 
       acc0[j] = mfma32(fa0[kk & 1], fb[st % 3], acc0[j]);
       acc1[j] = mfma32(fa1[kk & 1], fb[st % 3], acc1[j]);
     }
+    sg.next();
   }
 }
 
@@ -142,31 +208,30 @@ __global__ void __launch_bounds__(512, 1) wgrad2_kernel(const bf16_t* __restrict
   const int T = (L + BM - 1) / BM;
   const long NT = (long)B * T;
   const long t0 = NT * chunk / R, t1 = NT * (chunk + 1) / R;
+  const int nt = (int)(t1 - t0);
 
-  // issue the DMA of one tile into buffer `buf` (instructions dealt round-robin to the 8 waves)
-  auto stage = [&](long tile, unsigned char* buf) {
-    const int b = (int)(tile / T), t = (int)(tile - (tile / T) * T);
-    const int pos0 = t * BM;
-    const size_t sbase = (size_t)b * L * CH;
-    const int n = 16 + XR / 4;
-    for (int i = w; i < n; i += 8) {
-      if (i < 16) {                            // dy: 16 rows x 64 B per instruction
-        const int sub = i >> 3, row = (i & 7) * 16 + (lane >> 2);
-        const int pos = pos0 + row;
-        const void* src = pos < L ? (const void*)(dy + sbase + (size_t)pos * CH + half * 64 + sub * 32 + (lane & 3) * 8)
-                                  : (const void*)g_zero16;
-        glds16(src, buf + sub * (BM * 64) + (i & 7) * 1024);
-      } else {                                 // x: 4 rows x 256 B per instruction, swz256 image
-        const int j = i - 16, row = j * 4 + (lane >> 4);
-        const int chunk16 = (lane & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3));
-        const int pos = pos0 - halo + row;
-        const void* src = (pos >= -xlo && pos < L + xhi)
-                              ? (const void*)(x + ((ptrdiff_t)b * (L + xlo + xhi) + xlo + pos) * CH + chunk16 * 8)
-                              : (const void*)g_zero16;
-        glds16(src, buf + BM * 128 + j * 1024);
-      }
-    }
-  };
+  // this wave's DMA list, seeded once at tile t0 = (b0, tt0)
+  Stage2 sg;
+  {
+    const int b0 = (int)(t0 / T), tt0 = (int)(t0 - (long)b0 * T);
+    const int XS = L + xlo + xhi;                // rows per sample of x (CP halo rows around L)
+    sg.dys = (unsigned long)L * CH * 2;
+    sg.xs = (unsigned long)XS * CH * 2;
+    sg.dyb = (unsigned long)dy + (unsigned long)b0 * sg.dys + half * 128;
+    sg.xb = (unsigned long)x + (unsigned long)b0 * sg.xs + (unsigned long)((long)(xlo - halo) * (CH * 2));
+    sg.zero = opaque_addr(g_zero16);
+    sg.pos0 = tt0 * BM;
+    sg.L = L;
+    sg.n = 16 + XR / 4;
+    sg.w = w;
+    sg.xsh = xlo - halo;
+    sg.xspan = (unsigned)XS;
+    sg.rowdy = w * 16 + (lane >> 2);
+    sg.rowx = w * 4 + (lane >> 4);
+    const int chunk16 = (lane & 15) ^ ((((lane >> 4) & 3) << 2) | (w & 3));
+    sg.dyoff = (unsigned)(sg.rowdy * 256 + (lane & 3) * 16);
+    sg.xoff = (unsigned)(sg.rowx * 256 + chunk16 * 16);
+  }
 
   f32x16_t acc0[5], acc1[5];
 #pragma unroll
@@ -177,13 +242,13 @@ __global__ void __launch_bounds__(512, 1) wgrad2_kernel(const bf16_t* __restrict
   float bsum = 0.f;
   // bias partials: wave 0 -> co tile 0, wave 1 -> co tile 1 (summed from their A fragments)
   if (w == 0)
-    wgrad_tiles<5, 1>(smem, buf_bytes, t0, t1, stage, acc0, acc1, bsum, halo, d, 0, cig, lane);
+    wgrad_tiles<5, 1>(smem, buf_bytes, nt, sg, acc0, acc1, bsum, halo, d, 0, cig, lane);
   else if (w == 1)
-    wgrad_tiles<5, 2>(smem, buf_bytes, t0, t1, stage, acc0, acc1, bsum, halo, d, 0, cig, lane);
+    wgrad_tiles<5, 2>(smem, buf_bytes, nt, sg, acc0, acc1, bsum, halo, d, 0, cig, lane);
   else if (w < 4)
-    wgrad_tiles<5, 0>(smem, buf_bytes, t0, t1, stage, acc0, acc1, bsum, halo, d, 0, cig, lane);
+    wgrad_tiles<5, 0>(smem, buf_bytes, nt, sg, acc0, acc1, bsum, halo, d, 0, cig, lane);
   else
-    wgrad_tiles<4, 0>(smem, buf_bytes, t0, t1, stage, acc0, acc1, bsum, halo, d, 5, cig, lane);
+    wgrad_tiles<4, 0>(smem, buf_bytes, nt, sg, acc0, acc1, bsum, halo, d, 5, cig, lane);
   // tap-major slab [chunk][conv][k][co][ci]; lane -> ci (32 lanes = 128 contiguous bytes)
   float* dst = slab + ((size_t)chunk * nconv + cv) * KS * CH * CH + cig * 32 + r;
 #pragma unroll
@@ -308,6 +373,55 @@ PBX_EXPORT int pbx_wgrad2(const void* dy0, const void* dy1, const void* x, float
 // block's wgrad2 runs after every other backward kernel).
 namespace {
 constexpr int TBM = 128;   // source positions per tile
+constexpr int MAXET = 10;  // DMAs per wave per tile: ceil((rows0 / 4 + rows1 / 4 + 1) / 8), dil1 <= 6 (the LDS limit)
+
+// The DMA list of wave w for one tile of wgrad_tok: entry e is instruction i = w + 8 e of the tile's
+// n0 narrow dpre blocks, n1 wide dpre blocks (4 rows x 256 B each, swz256 image) and one token block.
+// Which block an entry is, its rows and its LDS destination are wave-uniform (scalar arithmetic on
+// constants of the unrolled entry index); a lane adds its row lane >> 4 and its permuted chunk, and a
+// tile moves only pos0 and the sample bases (b, t advance as a running pair, no division).
+struct StageTok {
+  unsigned long dyb0, dyb1, tokb;   // byte address of the sample's narrow / wide dpre row 0, of its first token
+  unsigned long dys, toks;          // bytes per sample
+  unsigned long zero, ones;         // the zero block; the "no token" block
+  int pos0, L;                      // first position of the tile to stage
+  int n0, n, w;                     // narrow blocks, narrow + wide blocks (= index of the token DMA); this wave
+  int hal1;
+  int lane, lrow;                   // per lane: lane, lane >> 4
+  unsigned lx;                      // per lane: chunk (lane & 15) permuted by the row's low bits
+
+  __device__ __forceinline__ void issue(int e, int nn, unsigned char* buf) const {
+    const int i = w + 8 * e;
+    if (i > nn) return;                          // (uniform)
+    if (i == n) {                                // tokens pos0 .. pos0 + 127: 2 per lane (L even)
+      const int p = pos0 + 2 * lane;
+      unsigned long a = tokb + (unsigned long)(unsigned)p * 8u;
+      asm volatile("" : "+v"(a));                // computed on every lane: the select below is a v_cndmask
+      glds16((const void*)(p < L ? a : ones), buf + n * 1024);
+      return;
+    }
+    const bool c = i >= n0;
+    const int j = c ? i - n0 : i;
+    const int r0 = pos0 - (c ? hal1 : KS / 2) + 4 * j;   // first row of the block (uniform, may be < 0)
+    const unsigned lo = (unsigned)(lrow * 256) + ((lx ^ (unsigned)(j & 3)) << 4);
+    unsigned long a = (c ? dyb1 : dyb0) + (unsigned long)((long)r0 * 256) + lo;
+    asm volatile("" : "+v"(a));                  // (as above: no EXEC-masked branch around the address)
+    glds16((const void*)((unsigned)(r0 + lrow) < (unsigned)L ? a : zero), buf + i * 1024);
+  }
+  __device__ __forceinline__ void all(unsigned char* buf) const {
+#pragma unroll
+    for (int e = 0; e < MAXET; ++e) issue(e, n, buf);
+  }
+  __device__ __forceinline__ void next() {
+    pos0 += TBM;
+    if (pos0 >= L) {
+      pos0 = 0;
+      dyb0 += dys;
+      dyb1 += dys;
+      tokb += toks;
+    }
+  }
+};
 
 // Workgroup: 8 waves, wave w = (conv w >> 2, 32-channel tile w & 3), 9 tap accumulators each.
 // LDS buffer (double-buffered, DMA-staged): narrow dpre rows [TBM + 8][256 B] | wide dpre rows
@@ -328,30 +442,29 @@ __global__ void __launch_bounds__(512, 1) wgrad_tok_kernel(const long long* __re
   const long NT = (long)B * T;
   const long t0 = NT * blockIdx.x / R, t1 = NT * (blockIdx.x + 1) / R;
 
-  auto stage = [&](long tile, unsigned char* buf) {
-    const int b = (int)(tile / T), t = (int)(tile - (tile / T) * T);
-    const int pos0 = t * TBM;
-    const size_t sbase = (size_t)b * L * CH;
-    const int n0 = rows0 / 4, n1 = rows1 / 4;
-    for (int i = w; i <= n0 + n1; i += 8) {
-      if (i == n0 + n1) {                      // tokens pos0 .. pos0 + 127: 2 per lane (L even)
-        const int p = pos0 + 2 * lane;
-        const void* src = p < L ? (const void*)(tok + (size_t)b * L + p) : (const void*)g_ones16;
-        glds16(src, buf + (rows0 + rows1) * 256);
-        continue;
-      }
-      const int c = i >= n0;
-      const int j = c ? i - n0 : i;
-      const int hal = c ? hal1 : hal0;
-      const bf16_t* dy = c ? dy1 : dy0;
-      const int row = j * 4 + (lane >> 4);
-      const int chunk16 = (lane & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3));
-      const int pos = pos0 - hal + row;
-      const void* src = (pos >= 0 && pos < L) ? (const void*)(dy + sbase + (size_t)pos * CH + chunk16 * 8)
-                                              : (const void*)g_zero16;
-      glds16(src, buf + (c ? rows0 * 256 : 0) + j * 1024);
-    }
-  };
+  const int nt = (int)(t1 - t0);
+
+  // this wave's DMA list, seeded once at tile t0 = (b0, tt0)
+  StageTok sg;
+  {
+    const int b0 = (int)(t0 / T), tt0 = (int)(t0 - (long)b0 * T);
+    sg.dys = (unsigned long)L * CH * 2;
+    sg.toks = (unsigned long)L * 8;
+    sg.dyb0 = (unsigned long)dy0 + (unsigned long)b0 * sg.dys;
+    sg.dyb1 = (unsigned long)dy1 + (unsigned long)b0 * sg.dys;
+    sg.tokb = (unsigned long)tok + (unsigned long)b0 * sg.toks;
+    sg.zero = opaque_addr(g_zero16);
+    sg.ones = opaque_addr(g_ones16);
+    sg.pos0 = tt0 * TBM;
+    sg.L = L;
+    sg.n0 = rows0 / 4;
+    sg.n = rows0 / 4 + rows1 / 4;
+    sg.w = w;
+    sg.hal1 = hal1;
+    sg.lane = lane;
+    sg.lrow = lane >> 4;
+    sg.lx = (unsigned)((lane & 15) ^ (((lane >> 4) & 3) << 2));
+  }
 
   f32x16_t acc[KS];
 #pragma unroll
@@ -370,17 +483,21 @@ __global__ void __launch_bounds__(512, 1) wgrad_tok_kernel(const long long* __re
     boff4[k] = cvb + swz256e(rb + 4, colb);
   }
   const int toff = (rows0 + rows1) * 256 + 8 * h * 8;   // this lane's 8 source tokens (int64) at k-step 0
-  if (t0 < t1) stage(t0, smem);
-  for (long tile = t0; tile < t1; ++tile) {
-    unsigned char* cur = smem + ((tile - t0) & 1) * buf_bytes;
-    unsigned char* nxt = smem + (((tile - t0) & 1) ^ 1) * buf_bytes;
+  if (nt > 0) {
+    sg.all(smem);
+    sg.next();
+  }
+  for (int it = 0; it < nt; ++it) {
+    unsigned char* cur = smem + (it & 1) * buf_bytes;
+    unsigned char* nxt = smem + ((it & 1) ^ 1) * buf_bytes;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of `cur` landed
     __syncthreads();                                   // ... every wave's; `nxt` no longer read
-    if (tile + 1 < t1) stage(tile + 1, nxt);
+    const int nn = it + 1 < nt ? sg.n : -1;            // last DMA of the next tile (issued in steps 0..)
     // (k-step kb, tap k) steps s = kb * 9 + k: the B fragment of step s + 2 is read while the MFMA of
     // step s runs (3-slot ring); the one-hot A operand of k-step kb + 1 (A[i = v][k = src] = [tok == v],
     // lane's v = r; positions >= L were staged as token -1) is built during taps 3..7 of k-step kb
     constexpr int NS = (TBM / 16) * KS;
+    static_assert(MAXET <= NS, "one DMA per step");
     bf16x8 fb[3], fa[2];
     unsigned tk[8];
     auto read_b = [&](int st) {
@@ -411,8 +528,11 @@ __global__ void __launch_bounds__(512, 1) wgrad_tok_kernel(const long long* __re
       if (k == 3 && kb + 1 < TBM / 16) read_tok(kb + 1);
       if (k == 7 && kb + 1 < TBM / 16) make_a(kb + 1);
       __builtin_amdgcn_sched_barrier(0);
+      // the next tile's DMA e = st (into `nxt`; retired by the vmcnt(0) above the next barrier)
+      if (st < MAXET) sg.issue(st, nn, nxt);
       acc[k] = mfma32(fa[kb & 1], fb[st % 3], acc[k]);
     }
+    sg.next();
   }
   // slab [R][2][KS][V][128]: D row = token v, column = channel
 #pragma unroll

@@ -149,7 +149,7 @@ def _grad_dst(p: torch.Tensor, shape) -> Tuple[torch.Tensor, bool]:
 
 
 # the first block's weight gradient is the last kernel of the backward (the main stream only has the
-# embedding / input-layer tail left beside it): it takes every CU (the other blocks' take 7/8)
+# embedding / input-layer tail left beside it): it takes every CU (the other blocks' take WGRAD_CU_EIGHTHS / 8)
 WGRAD_TAIL_FULL = True
 # the local-MLP dWl / dbl slab folds run on the weight-gradient stream (False: on the main
 # stream right after the LN2 / MLP backward kernel)
@@ -163,8 +163,11 @@ DGRAD_FIN = True
 INPUT_BWD_EARLY = True
 
 
-# eighths of the CUs the aux-stream conv weight gradient takes (R = 56 chunks at 7 on 256 CUs)
-WGRAD_CU_EIGHTHS = 7
+# eighths of the CUs the aux-stream conv weight gradient takes (R = 64 chunks at 8 on 256 CUs, 56 at 7).
+# The kernels beside it fill a CU's registers, so sharing the chip with them is a CU partition whatever the
+# share; with the in-loop tile staging 8 measured fastest on the step (8 > 7 > 6 in every round of a same-box
+# A/B, +0.2 % over 7: profiles/r7/wgrad_staging_ab.txt; the 600 us kernel before it was tuned to 7)
+WGRAD_CU_EIGHTHS = 8
 
 
 def _wgrad(dy0: torch.Tensor, dy1: Optional[torch.Tensor], x: torch.Tensor, KS: int, dil: int, nconv: int,
@@ -173,9 +176,8 @@ def _wgrad(dy0: torch.Tensor, dy1: Optional[torch.Tensor], x: torch.Tensor, KS: 
     them alive while the launch may still be running on another stream)."""
     dev = x.device
     ntiles = B * ((L + 127) // 128)
-    # csrc/wgrad.hip: one workgroup per CU, R chunks x (nconv x 2) channel halves = 7/8 of the CUs
-    # (R = 56 on 256 CUs): the aux-stream weight gradient runs beside the main-stream backward, and
-    # leaving it a few CUs measured +2.4 % on the step over R = 64 (R = 48: +1.3 %, 32: -0.4 %)
+    # csrc/wgrad.hip: one workgroup per CU, R chunks x (nconv x 2) channel halves = WGRAD_CU_EIGHTHS / 8
+    # of the CUs; the aux-stream weight gradient runs beside the main-stream backward
     R = max(8, (WGRAD_CU_EIGHTHS * _num_cus(dev) // (16 * nconv)) // 8 * 8)
     if full_chip:
         R = max(8, (_num_cus(dev) // (2 * nconv)) // 8 * 8)
