@@ -88,29 +88,44 @@ def pretrain_main(argv: Optional[List[str]] = None) -> dict:
     B, L = cfg.train.batch_size, cfg.model.sequences_length
     corr = CorruptionParams(cfg.data.token_corruption_p, cfg.data.annotation_positive_p,
                             cfg.data.annotation_negative_p, cfg.data.blank_annotation_p)
-    if cfg.data.source == "synthetic" and cfg.data.lengths:
-        from ..data.synthetic import MultiLengthSynthetic
-        loader = MultiLengthSynthetic(cfg.data.lengths, cfg.model.num_annotations, B, dev,
-                                      seed=cfg.data.seed + 1000 * info.rank, min_length=cfg.data.min_length,
-                                      density=cfg.data.annotation_density, corruption=corr)
-    elif cfg.data.source == "synthetic":
-        loader = SyntheticUniRefGO(L, cfg.model.num_annotations, B, dev, min_length=cfg.data.min_length,
-                                   max_length=cfg.data.max_length, density=cfg.data.annotation_density,
-                                   seed=cfg.data.seed + 1000 * info.rank, corruption=corr)
-    elif cfg.data.source in ("store", "hdf5"):
-        from ..train.dataloaders import create_pretrain_dataloaders
-        loader = create_pretrain_dataloaders(cfg.data.path, B, recursive_dir=True, num_workers=cfg.data.num_workers,
-                                             seq_max_length=L, device=dev, seed=cfg.data.seed)
-    elif cfg.data.source == "dataframe":
-        from torch.utils.data import DataLoader
-        from ..data import UniRefGO_PretrainingDataset, collate_triples
-        from ..parallel.sampler import ShardedSampler
-        ds = UniRefGO_PretrainingDataset(_DataFrameAnnotations.load(cfg.data.path, cfg.model.num_annotations),
-                                         seq_max_length=L)
-        loader = DataLoader(ds, batch_size=B, sampler=ShardedSampler(len(ds), info.rank, info.world_size),
-                            num_workers=cfg.data.num_workers, collate_fn=collate_triples, drop_last=True)
-    else:
+
+    def make_loader(path, seed):
+        if cfg.data.source == "synthetic" and cfg.data.lengths:
+            from ..data.synthetic import MultiLengthSynthetic
+            return MultiLengthSynthetic(cfg.data.lengths, cfg.model.num_annotations, B, dev,
+                                        seed=seed + 1000 * info.rank, min_length=cfg.data.min_length,
+                                        density=cfg.data.annotation_density, corruption=corr)
+        if cfg.data.source == "synthetic":
+            return SyntheticUniRefGO(L, cfg.model.num_annotations, B, dev, min_length=cfg.data.min_length,
+                                     max_length=cfg.data.max_length, density=cfg.data.annotation_density,
+                                     seed=seed + 1000 * info.rank, corruption=corr)
+        if cfg.data.source in ("store", "hdf5"):
+            from ..train.dataloaders import create_pretrain_dataloaders
+            return create_pretrain_dataloaders(path, B, recursive_dir=True, num_workers=cfg.data.num_workers,
+                                               seq_max_length=L, device=dev, seed=seed)
+        if cfg.data.source == "dataframe":
+            from torch.utils.data import DataLoader
+            from ..data import UniRefGO_PretrainingDataset, collate_triples
+            from ..parallel.sampler import ShardedSampler
+            ds = UniRefGO_PretrainingDataset(_DataFrameAnnotations.load(path, cfg.model.num_annotations),
+                                             seq_max_length=L)
+            return DataLoader(ds, batch_size=B, sampler=ShardedSampler(len(ds), info.rank, info.world_size),
+                              num_workers=cfg.data.num_workers, collate_fn=collate_triples, drop_last=True)
         raise ValueError(f"unknown data.source {cfg.data.source!r}")
+
+    loader = make_loader(cfg.data.path, cfg.data.seed)
+    # held-out evaluation (eval.every > 0): the same source read from eval.path; the synthetic source gets a
+    # second generator of its own seed (endless: eval.batches bounds it, 8 by default)
+    eval_loader, eval_batches = None, cfg.eval.batches
+    if cfg.eval.every > 0:
+        if cfg.data.source == "synthetic":
+            eval_loader = make_loader(None, cfg.eval.seed)
+            eval_batches = 8 if eval_batches is None else eval_batches
+        elif cfg.eval.path is None:
+            raise ValueError("eval.every > 0 needs eval.path (the held-out data) for data.source "
+                             f"{cfg.data.source!r}")
+        else:
+            eval_loader = make_loader(cfg.eval.path, cfg.data.seed)
     opt = torch.optim.Adam(model.parameters(), lr=cfg.optim.lr, betas=cfg.optim.betas, eps=cfg.optim.eps,
                            weight_decay=cfg.optim.weight_decay)
     from ..train.pretrain import pretrain
@@ -122,10 +137,15 @@ def pretrain_main(argv: Optional[List[str]] = None) -> dict:
                    tensorboard_dir=a.tensorboard,
                    resume=a.resume, profile_steps=a.profile_steps, profile_dir=a.profile_dir,
                    zero_optimizer=a.zero, comm_dtype=cfg.dist.comm_dtype,
-                   dp_batch_softmax=cfg.dist.dp_batch_softmax)
+                   dp_batch_softmax=cfg.dist.dp_batch_softmax, eval_dataloader=eval_loader,
+                   eval_every=cfg.eval.every, eval_batches=eval_batches)
     if info.is_main:
-        print(json.dumps({"final_loss": res["train_loss"][-1] if res["train_loss"] else None,
-                          "iterations": len(res["train_loss"]), "final_model": res.get("final_model_path")}))
+        out = {"final_loss": res["train_loss"][-1] if res["train_loss"] else None,
+               "iterations": len(res["train_loss"]), "final_model": res.get("final_model_path")}
+        if res.get("eval"):
+            from ..train.evaluate import scalar_metrics
+            out["eval"] = scalar_metrics(res["eval"][-1])
+        print(json.dumps(out))
     return res
 
 

@@ -99,6 +99,14 @@ class TrainConfig:
 
 
 @dataclass
+class EvalConfig:
+    every: int = 0                      # held-out evaluation every N steps and after the last (0: off)
+    batches: Optional[int] = None       # batches per evaluation (None: the whole loader; synthetic: 8)
+    path: Optional[str] = None          # held-out store / CSV, read as data.source says (synthetic: unused)
+    seed: int = 12345                   # synthetic source: the seed of the held-out generator
+
+
+@dataclass
 class RunConfig:
     model: ModelConfig = field(default_factory=ModelConfig)
     data: DataConfig = field(default_factory=DataConfig)
@@ -106,6 +114,7 @@ class RunConfig:
     dist: DistConfig = field(default_factory=DistConfig)
     kernel: KernelConfig = field(default_factory=KernelConfig)
     train: TrainConfig = field(default_factory=TrainConfig)
+    eval: EvalConfig = field(default_factory=EvalConfig)
     name: str = "custom"
 
     def to_dict(self) -> Dict[str, Any]:

@@ -21,6 +21,12 @@
 // PyTorch's log clamp (>= -100), weighted by w[b] / (B A); writes dz = dL/dz (bf16, the operand of
 // the backward GEMMs), per-(row tile, column) partial sums of dz (the bias gradient, folded by the
 // caller) and per-workgroup loss partials.  z itself is never stored.
+//
+// EPI_GO_EVAL: the same head for a held-out evaluation (ops/eval_heads.py): the same main loop, tile
+// transpose, sigmoid / clamped-log BCE expression and weighting, but no dz and no bias partials; every
+// entry with weight > 0 is counted into one of two per-workgroup LDS histograms of 256 bins of p (y = 1 /
+// y = 0, bin = min(255, (int)(p * 256))) with LDS integer atomics, and each workgroup stores its 2 x 256
+// bins to its own row of a partial buffer (no global atomics: results are bitwise repeatable).
 #include "mfma.h"
 
 using namespace pbx;
@@ -31,7 +37,8 @@ constexpr int BT = 128;   // tile rows / cols
 constexpr int BK = 128;   // K chunk
 constexpr int TILE = BT * 256;   // bytes of one staged operand tile
 
-enum { EPI_STORE = 0, EPI_GO = 1 };
+enum { EPI_STORE = 0, EPI_GO = 1, EPI_GO_EVAL = 2 };
+constexpr int GO_BINS = 256;   // EPI_GO_EVAL: histogram bins of p per class
 
 struct GoArgs {
   const float* bias;      // [N]
@@ -44,6 +51,7 @@ struct GoArgs {
   float* dbias_part;      // [ceil(M / BT)][N]
   float* loss_part;       // [gridDim.x * gridDim.y]
   float inv_mn;           // 1 / (M N)
+  unsigned* hist_part;    // EPI_GO_EVAL: [gridDim.x * gridDim.y][2 * GO_BINS]
 };
 
 // One operand tile (rows r0.., K chunk k0..) into LDS.  KMAJ: K runs along memory (A row / B col) ->
@@ -208,7 +216,12 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const bf16_t* __restrict__
     // 8-column group (tid & 15) over 8 rows -> column sums in registers, folded over the 16 row groups
     constexpr int TS = BT + 4;
     float* ft = reinterpret_cast<float*>(smem);
+    unsigned* hist = reinterpret_cast<unsigned*>(ft + BT * TS);   // EPI_GO_EVAL: [2][GO_BINS] behind the tile
     __syncthreads();                                  // staging tiles no longer read
+    if constexpr (EPI == EPI_GO_EVAL) {
+      hist[tid] = 0u;
+      hist[tid + GO_BINS] = 0u;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -260,9 +273,16 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const bf16_t* __restrict__
         const float lp = fmaxf(__logf(p), -100.f), l1p = fmaxf(__logf(1.0f - p), -100.f);
         const bool ok = nb + e < N;
         lsum += ok ? wv[e] * -(yy[e] * lp + (1.0f - yy[e]) * l1p) * go.inv_mn : 0.f;
-        const float pq = p * (1.0f - p);
-        g[e] = ok ? wv[e] * go.inv_mn * (p - yy[e]) * pq / fmaxf(pq, 1e-12f) : 0.f;
+        if constexpr (EPI == EPI_GO_EVAL) {
+          // p in [0, 1] and p * 256 is exact, so the bin edges are exactly k / 256 (0.5 = bin 128)
+          if (ok && wv[e] > 0.f)
+            atomicAdd(hist + (yy[e] > 0.5f ? 0 : GO_BINS) + min(GO_BINS - 1, (int)(p * (float)GO_BINS)), 1u);
+        } else {
+          const float pq = p * (1.0f - p);
+          g[e] = ok ? wv[e] * go.inv_mn * (p - yy[e]) * pq / fmaxf(pq, 1e-12f) : 0.f;
+        }
       }
+      if constexpr (EPI == EPI_GO_EVAL) continue;
       const uint4 q = packq8(g);
       if (dzv && nb + 8 <= go.lddz) {                // pad columns [N, lddz) are written as zeros
         *reinterpret_cast<uint4*>(go.dz + (size_t)m * go.lddz + nb) = q;
@@ -279,15 +299,22 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const bf16_t* __restrict__
     }
     // column sums over the 16 row groups: through LDS (reuse the tile after a barrier)
     __syncthreads();
+    if constexpr (EPI == EPI_GO_EVAL) {
+      // this workgroup's 2 x 256 bins -> its own row of the partial buffer
+      unsigned* dst = go.hist_part + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * (2 * GO_BINS);
+      dst[tid] = hist[tid];
+      dst[tid + GO_BINS] = hist[tid + GO_BINS];
+    } else {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) ft[rg * TS + 8 * c8 + e] = dcol[e];
-    __syncthreads();
-    if (tid < BT) {
-      float a = 0.f;
+      for (int e = 0; e < 8; ++e) ft[rg * TS + 8 * c8 + e] = dcol[e];
+      __syncthreads();
+      if (tid < BT) {
+        float a = 0.f;
 #pragma unroll
-      for (int k = 0; k < 16; ++k) a += ft[k * TS + tid];
-      const int n = n0 + tid;
-      if (n < N) go.dbias_part[(size_t)blockIdx.y * N + n] = a;
+        for (int k = 0; k < 16; ++k) a += ft[k * TS + tid];
+        const int n = n0 + tid;
+        if (n < N) go.dbias_part[(size_t)blockIdx.y * N + n] = a;
+      }
     }
     float* red = ft + 16 * TS;
     const float lt = block_sum256(lsum, red);
@@ -386,7 +413,9 @@ int launch_batch(const GemmBatch& gb, int n, int accumulate, hipStream_t st) {
 template <int TA, int TB, bool AL_A, bool AL_B, int EPI>
 int launch(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, int K, int splitk,
            int accumulate, const GoArgs& go, hipStream_t st) {
-  constexpr int lds = EPI == EPI_GO ? BT * (BT + 4) * 4 : 2 * TILE;     // GO: the fp32 tile for the epilogue
+  // GO: the fp32 tile for the epilogue; GO_EVAL: + the two histograms (69632 B: two workgroups per CU)
+  constexpr int lds = EPI == EPI_GO ? BT * (BT + 4) * 4
+                      : EPI == EPI_GO_EVAL ? BT * (BT + 4) * 4 + 2 * GO_BINS * 4 : 2 * TILE;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)gemm_kernel<TA, TB, AL_A, AL_B, EPI>,
@@ -450,9 +479,22 @@ PBX_EXPORT int pbx_go_head_fused(const void* x, long ldx, const void* w, long ld
                                  long ldy, const float* wrow, const float* wfull, void* dz, long lddz, float* dbias_part,
                                  float* loss_part, int M, int N, int K, hipStream_t st) {
   if (M <= 0 || N <= 0 || K <= 0 || (wrow == nullptr) == (wfull == nullptr)) return (int)hipErrorInvalidValue;
-  GoArgs go{bias, y, ldy, wrow, wfull, (bf16_t*)dz, lddz, dbias_part, loss_part, 1.0f / ((float)M * (float)N)};
+  GoArgs go{bias, y, ldy, wrow, wfull, (bf16_t*)dz, lddz, dbias_part, loss_part, 1.0f / ((float)M * (float)N),
+            nullptr};
   const bool aa = aligned(x, ldx, K, false), ab = aligned(w, ldw, K, false);
   return dispatch_al<0, 1, EPI_GO>(aa, ab, x, ldx, w, ldw, nullptr, 0, M, N, K, 1, 0, go, st);
+}
+
+// The GO head for a held-out evaluation (EPI_GO_EVAL): operands, targets and weights as pbx_go_head_fused;
+// outputs loss_part [tiles] (each already divided by B A) and hist_part [tiles][2][256] (bins of p over the
+// entries with weight > 0: y = 1, then y = 0), tiles = ceil(B / 128) ceil(A / 128).
+PBX_EXPORT int pbx_go_head_eval(const void* x, long ldx, const void* w, long ldw, const float* bias, const float* y,
+                                long ldy, const float* wrow, const float* wfull, float* loss_part,
+                                unsigned* hist_part, int M, int N, int K, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || (wrow == nullptr) == (wfull == nullptr)) return (int)hipErrorInvalidValue;
+  GoArgs go{bias, y, ldy, wrow, wfull, nullptr, 0, nullptr, loss_part, 1.0f / ((float)M * (float)N), hist_part};
+  const bool aa = aligned(x, ldx, K, false), ab = aligned(w, ldw, K, false);
+  return dispatch_al<0, 1, EPI_GO_EVAL>(aa, ab, x, ldx, w, ldw, nullptr, 0, M, N, K, 1, 0, go, st);
 }
 
 // n (<= 4) GEMMs C_i (+)= op(A_i) op(B_i) of one (ta, tb) class in one launch (no split-K).

@@ -15,7 +15,12 @@ files and keys.  Differences (all additive):
   reference syncs every step);
 * resume restores RNG state and attention heads (``extra_state``);
 * fault injection (``PBX_FAULT_AT_STEP``) and automatic resume from the latest
-  checkpoint (``resume="latest"``) for elastic restarts.
+  checkpoint (``resume="latest"``) for elastic restarts;
+* held-out evaluation (``eval_dataloader`` / ``eval_every`` / ``eval_batches``): every ``eval_every`` steps
+  and after the last one, :func:`.evaluate.evaluate_pretrain` runs on the held-out loader -- the metrics the
+  reference's docstring promises and its commented-out lines (``utils.py:303-304``) never produced.  With
+  ``eval_every=0`` (the default) nothing changes; with it on, the training run itself is unchanged too
+  (parameters, optimizer, scheduler, loader cursor and RNG streams are what they would have been).
 """
 from __future__ import annotations
 
@@ -62,6 +67,27 @@ def _maybe_fuse_optimizer(model, optimizer) -> torch.optim.Optimizer:
     return fused
 
 
+def _evaluate(model, loader, max_batches, device, compute_dtype, info, step, metrics, tb) -> Dict[str, Any]:
+    """One held-out evaluation inside the training loop; the RNG streams are put back afterwards (a
+    ``DataLoader`` iterator draws its base seed from the global generator).  The plateau scheduler keeps
+    using the training loss."""
+    from .evaluate import evaluate_pretrain, scalar_metrics
+    rng = rng_state(device)
+    m = evaluate_pretrain(model, loader, max_batches=max_batches, device=device, compute_dtype=compute_dtype,
+                          distributed=info.distributed)
+    set_rng_state(rng, device)
+    sc = scalar_metrics(m)
+    if info.is_main:
+        logging.info(f"Current batch iteration: {step} | Eval loss: {sc['loss']:.4f} | "
+                     f"Token accuracy: {sc['token_accuracy']:.4f} | "
+                     f"Masked token accuracy: {sc['masked_token_accuracy']:.4f} | "
+                     f"GO F1: {sc['go_f1']:.4f} | GO AUROC: {sc['go_auroc']:.4f}")
+        metrics.write(step=step, **{f"eval_{k}": v for k, v in sc.items()})
+        if tb is not None:
+            tb.add_scalars({f"eval/{k}": v for k, v in sc.items() if not k.startswith("n_")}, step)
+    return {"step": step, **m}
+
+
 def pretrain(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Optimizer,
              local_loss_fn: Optional[torch.nn.Module] = None, global_loss_fn: Optional[torch.nn.Module] = None,
              max_batch_iterations: int = 250, save_path: str = ".", nb_iterations_checkpoint: int = 1000,
@@ -72,7 +98,8 @@ def pretrain(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
              fuse_optimizer: bool = True, final_save: bool = True, profile_steps: Optional[str] = None,
              profile_dir: Optional[str] = None, zero_optimizer: bool = False,
              comm_dtype="fp32", tensorboard_dir: Optional[str] = None,
-             dp_batch_softmax: bool = False) -> Dict[str, Any]:
+             dp_batch_softmax: bool = False, eval_dataloader=None, eval_every: int = 0,
+             eval_batches: Optional[int] = None) -> Dict[str, Any]:
     info = pdist.init_distributed()
     if device is None:
         device = info.device
@@ -81,6 +108,9 @@ def pretrain(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
     if fuse_optimizer:
         optimizer = _maybe_fuse_optimizer(model, optimizer)
     results: Dict[str, Any] = {"train_loss": [], "optimizer": optimizer}
+    do_eval = eval_dataloader is not None and eval_every > 0
+    if do_eval:
+        results["eval"] = []
 
     ddp = None
     if info.distributed:
@@ -210,6 +240,11 @@ def pretrain(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
                 loss_acc.zero_()
                 parts_acc.zero_()
                 n_acc = 0
+            if do_eval and (current % eval_every == 0 or current >= max_batch_iterations):
+                t_eval = time.time()
+                results["eval"].append(_evaluate(model, eval_dataloader, eval_batches, device, compute_dtype, info,
+                                                 current, metrics, tb))
+                t_last += time.time() - t_eval          # the logged step time stays the training steps' own
             if current >= max_batch_iterations:
                 break
             if current % nb_iterations_checkpoint == 0:
