@@ -16,7 +16,8 @@ from typing import Dict, Tuple
 import torch
 import torch.nn.functional as F
 
-from .global_track import FusedGlobalBlockFn, GlobalBlockFn, HeadsLossFn, InputLayerFn, glob_fused_ok, pack_batch
+from .global_track import (FusedGlobalBlockFn, GlobalBlockFn, HeadsLossFn, InputLayerFn, bf16_of, glob_fused_ok,
+                           pack_batch)
 from . import local_track as _lt
 from .local_track import CH, EmbedFn, conv_images, embed_tokens, local_block, wgrad_tok_ok
 from .paper_track import PaperHeadsLossFn, paper_block, unit_attention_weight
@@ -100,6 +101,14 @@ def fused_encode(model, tokens: torch.Tensor, annotations: torch.Tensor,
         else:
             glob_imgs.append(None)
     pack_batch(items)
+    # the first block's conv as token-table row sums (csrc/conv_tok.hip): the tables follow this step's weight
+    # images and embedding
+    tok_tab = None
+    if h is None:
+        nc0 = blocks[0].local_narrow_conv_layer[0]
+        if _lt.conv_tok_ok(tok_c.shape[0], tok_c.shape[1], nc0.weight.shape[2], blocks[0].wide_conv_dilation,
+                           emb_w.shape[0]):
+            tok_tab = _lt.conv_tok_tables(conv_imgs[0][0], conv_imgs[0][2], bf16_of(emb_w))
     for i, blk in enumerate(blocks):
         att = blk.global_attention_layer
         if paper:
@@ -115,7 +124,7 @@ def fused_encode(model, tokens: torch.Tensor, annotations: torch.Tensor,
             first = i == 0 and cp is None
             h, vpart = local_block(h, gb, blk, conv_imgs[i], tail=(i == 0), cp=cp,
                                    tok=tok_c if first else None, emb=emb_w if first else None,
-                                   emb_grad=fold and i == 0)
+                                   emb_grad=fold and i == 0, tok_tab=tok_tab if i == 0 else None)
             if cp is not None:
                 vpart = cp.pool_sum(vpart)      # [B, 1, NJ]: the group-wide sum over every shard's tiles
             wp = att.W_parameter

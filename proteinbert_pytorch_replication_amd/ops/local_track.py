@@ -1,10 +1,11 @@
 """Autograd wrappers of the fused CDNA4 local-track kernels (``csrc/conv2.hip``, ``csrc/conv4.hip``,
-``csrc/wgrad.hip``, ``csrc/ln.hip``, ``csrc/pool.hip``).
+``csrc/conv_tok.hip``, ``csrc/wgrad.hip``, ``csrc/ln.hip``, ``csrc/pool.hip``).
 
 One :class:`LocalBlockFn` call is the whole local track of one ``ProteinBERTBlock`` in reference
 semantics (reference ``ProteinBERT/modules.py:201-219``)::
 
-    s1 = x + GELU(conv_d1(x)) + GELU(conv_d5(x)) + gb       (conv_fwd3: 1 launch)
+    s1 = x + GELU(conv_d1(x)) + GELU(conv_d5(x)) + gb       (conv_fwd5 / conv_fwd3: 1 launch; the first block,
+                                                              whose x is the embedding: conv_fwd_tok)
     h1 = LN_(L,C)(s1); s2 = h1 + GELU(h1 Wl^T + bl)           (ln_linear_fwd: 1 launch)
     h2 = LN_(L,C)(s2); vpart = sum_tile GELU(h2 Wv_cat^T)     (pool_fwd, csrc/pool.hip: 1 launch)
 
@@ -54,6 +55,9 @@ _lib.register("pbx_conv_dgrad4f", [_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _
                                     _F, _P])
 _lib.register("pbx_embed_dpre", [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P])
 _lib.register("pbx_embed_bwd_groups", [_L])
+_lib.register("pbx_conv_fwd_tok_ok", [_I, _I, _I, _I, _I])
+_lib.register("pbx_conv_tok_tables", [_P, _P, _P, _P, _I, _P])
+_lib.register("pbx_conv_fwd_tok", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P])
 
 CH = 128          # kernels are specialised for local_dim = 128
 PB = 32           # positions per workgroup of the position-major LayerNorm kernels
@@ -209,6 +213,52 @@ EMBED_FOLD = True
 EMBED_GATHER = True
 
 
+# ... and that conv is nine table rows per output instead of a GEMM (csrc/conv_tok.hip: the input takes at most
+# 32 distinct values, so T[k][v] = bf16(W[:, :, k]) bf16(E[v]) is built once per step and the forward sums rows
+# T[k][tok[pos + (k - 4) d]]); its LayerNorm-1 partials are per (8 positions, 64-channel half), which
+# the consumers merge as (T1, BM1) = (L / 4, 4).  Where the kernel declines (L not a multiple of 128) or
+# PBX_CONV_TOK=0: pbx_conv_fwd3t (conv_fwd over x where the embedding output is materialised).
+CONV_TOK = os.environ.get("PBX_CONV_TOK", "1") == "1"
+
+
+def conv_tok_ok(B: int, L: int, KS: int, dil: int, V: int) -> bool:
+    return CONV_TOK and bool(_lib.lib().pbx_conv_fwd_tok_ok(B, L, KS, dil, V))
+
+
+def conv_tok_tables(wpn: torch.Tensor, wpw: torch.Tensor, emb_b: torch.Tensor) -> torch.Tensor:
+    """The first block's token tables ``[half 2][conv 2][tap 9][V + 1][64]`` fp32 (row V: zeros, the padding)
+    from the forward weight images (:func:`pack_conv` / pack_batch) and the bf16 embedding ``[V, 128]``."""
+    V = emb_b.shape[0]
+    tab = torch.empty((2, 2, 9, V + 1, CH // 2), dtype=torch.float32, device=emb_b.device)
+    _lib.call("pbx_conv_tok_tables", wpn.data_ptr(), wpw.data_ptr(), emb_b.data_ptr(), tab.data_ptr(), V,
+              _lib.stream_ptr(emb_b.device))
+    return tab
+
+
+def conv_fwd_first(tok, emb_b, wpn, wpw, bn, bw, gb, pre_n, pre_w, s1, KS, dil, stream, tok_tab=None):
+    """The first block's conv forward over ``x = emb_b[tok]`` (never materialised): the token-table kernel where
+    it takes the shape, else ``pbx_conv_fwd3t``.  ``pre_n`` / ``pre_w``: GELU' outputs or None (no backward);
+    ``tok_tab``: this step's :func:`conv_tok_tables`, built here when None.  Returns ``(st1, T1, bm1)``: the
+    LayerNorm-1 (mean, M2) partials ``[B, T1, 2]``, each counting ``bm1 x 128`` elements."""
+    B, L = tok.shape
+    V = emb_b.shape[0]
+    if conv_tok_ok(B, L, KS, dil, V):
+        T1, bm1 = L // 4, 4                     # one partial per 8 positions x 64 channels (= 4 x 128 elements)
+        st1 = torch.empty((B, T1, 2), dtype=torch.float32, device=tok.device)
+        if tok_tab is None:
+            tok_tab = conv_tok_tables(wpn, wpw, emb_b)
+        _lib.call("pbx_conv_fwd_tok", tok.data_ptr(), emb_b.data_ptr(), tok_tab.data_ptr(), bn.data_ptr(),
+                  bw.data_ptr(), gb.data_ptr(), _p(pre_n), _p(pre_w), s1.data_ptr(), st1.data_ptr(), B, L, KS, dil, V,
+                  stream)
+    else:
+        T1, bm1 = (L + BM1 - 1) // BM1, BM1
+        st1 = torch.empty((B, T1, 2), dtype=torch.float32, device=tok.device)
+        _lib.call("pbx_conv_fwd3t", tok.data_ptr(), emb_b.data_ptr(), wpn.data_ptr(), wpw.data_ptr(), bn.data_ptr(),
+                  bw.data_ptr(), gb.data_ptr(), _p(pre_n), _p(pre_w), s1.data_ptr(), st1.data_ptr(), B, L, KS, dil,
+                  stream)
+    return st1, T1, bm1
+
+
 def wgrad_tok_ok(tok: Optional[torch.Tensor], emb: Optional[torch.Tensor], L: int, KS: int) -> bool:
     return (WGRAD_TOK and tok is not None and emb is not None and KS == 9 and L % 2 == 0
             and emb.shape[0] <= 32 and emb.shape[1] == CH and tok.dtype == torch.int64 and tok.is_contiguous())
@@ -259,14 +309,15 @@ class LocalBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gb, wn, bn, ww, bw, g1, be1, wl, bl, g2, be2, wv_bf16, dil: int, packed=None,
-                tail: bool = False, cp=None, tok=None, emb=None, emb_grad: bool = False):
+                tail: bool = False, cp=None, tok=None, emb=None, emb_grad: bool = False, tok_tab=None):
         """``packed``: (wpn, wtn, wpw, wtw) weight images already built for this step (pack_batch);
         ``tail``: the first block (its backward ends the step: the conv weight gradient gets every CU);
         ``cp``: a :class:`..parallel.cp_fused.CPShard` -- ``x`` is this rank's slice of the sequence, the
         conv reads the neighbours' halo rows and the (L, C) LayerNorm statistics are group-wide;
         ``tok`` / ``emb``: ``x`` is the embedding bf16(emb[tok]) (the first block): the conv weight gradient
         goes through the token one-hot (:func:`_wgrad_tok`); ``emb_grad``: ``x`` carries no autograd
-        history and the backward returns ``emb``'s gradient instead of ``x``'s (:data:`EMBED_FOLD`)."""
+        history and the backward returns ``emb``'s gradient instead of ``x``'s (:data:`EMBED_FOLD`);
+        ``tok_tab``: this step's :func:`conv_tok_tables`, when the caller built them (with ``x`` None)."""
         params = (wn, bn, ww, bw, g1, be1, wl, bl, g2, be2)
         ctx.cp = cp
         if cp is not None:
@@ -288,7 +339,7 @@ class LocalBlockFn(torch.autograd.Function):
         KS = wn.shape[2]
         dev = xt.device
         stream = _lib.stream_ptr(dev)
-        T1 = (L + BM1 - 1) // BM1
+        T1, bm1 = (L + BM1 - 1) // BM1, BM1
         T2 = (L + PB - 1) // PB
         if packed is not None:
             wpn, wtn, wpw, wtw = packed
@@ -302,25 +353,31 @@ class LocalBlockFn(torch.autograd.Function):
         pre_n = torch.empty_like(xt) if need_bwd else None
         pre_w = torch.empty_like(xt) if need_bwd else None
         s1 = torch.empty_like(xt)
-        st1 = torch.empty((B, T1, 2), dtype=torch.float32, device=dev)
         gb = gb.detach().float().contiguous()
-        if x is None:
-            x_ext, hlo = None, 0
+        # the block's input is known to be bf16(emb[tok]): the conv forward needs no x.  Also taken when x is
+        # materialised (EMBED_FOLD / EMBED_GATHER off) and the token-table kernel takes the shape, so the
+        # forward is the same bits whichever way the backward goes
+        from_tok = x is None or (cp is None and tok is not None and emb is not None and tok.dtype == torch.int64
+                                 and tok.is_contiguous() and tuple(tok.shape) == (B, L) and emb.shape[1] == CH
+                                 and conv_tok_ok(B, L, KS, dil, emb.shape[0]))
+        if from_tok:
+            x_ext, hlo = x, 0
             emb_b = bf16_of(emb)                  # the optimizer-maintained bf16 mirror: no cast launch
-            _lib.call("pbx_conv_fwd3t", tok.data_ptr(), emb_b.data_ptr(), wpn.data_ptr(), wpw.data_ptr(),
-                      bn.data_ptr(), bw.data_ptr(), gb.data_ptr(), _p(pre_n), _p(pre_w), s1.data_ptr(),
-                      st1.data_ptr(), B, L, KS, dil, stream)
+            st1, T1, bm1 = conv_fwd_first(tok, emb_b, wpn, wpw, bn, bw, gb, pre_n, pre_w, s1, KS, dil, stream,
+                                          tok_tab)
         elif cp is None:
             x_ext, hlo = x, 0
+            st1 = torch.empty((B, T1, 2), dtype=torch.float32, device=dev)
             conv_fwd(x, wpn, wpw, bn, bw, gb, pre_n, pre_w, s1, st1, B, L, KS, dil, stream)
         else:
             x_ext, hlo = cp.halo_rows(x), cp.halo
+            st1 = torch.empty((B, T1, 2), dtype=torch.float32, device=dev)
             conv_fwd(x_ext, wpn, wpw, bn, bw, gb, pre_n, pre_w, s1, st1, B, L, KS, dil, stream, hlo, hlo)
             cp.fix_stats(st1, BM1)
         pre_l = torch.empty_like(xt) if need_bwd else None
         s2 = torch.empty_like(xt)
         st2 = torch.empty((B, T2, 2), dtype=torch.float32, device=dev)
-        _lib.call("pbx_ln_linear_fwd", s1.data_ptr(), st1.data_ptr(), T1, BM1, g1.data_ptr(), be1.data_ptr(),
+        _lib.call("pbx_ln_linear_fwd", s1.data_ptr(), st1.data_ptr(), T1, bm1, g1.data_ptr(), be1.data_ptr(),
                   wl_b.data_ptr(), bl.data_ptr(), _p(pre_l), s2.data_ptr(), st2.data_ptr(), B, L, LN_EPS, stream)
         if cp is not None:
             cp.fix_stats(st2, PB)
@@ -338,6 +395,7 @@ class LocalBlockFn(torch.autograd.Function):
         if ctx.emb_grad and (ctx.tok is None or (x is not None and x.requires_grad)):
             raise ValueError("emb_grad needs a token-embedding input without autograd history (wgrad_tok_ok)")
         ctx.meta = (B, L, KS, dil, T1, T2, NJ)
+        ctx.bm1 = bm1
         ctx.tail = bool(tail) and WGRAD_TAIL_FULL
         ctx.set_materialize_grads(False)
         ctx.params = params
@@ -351,6 +409,7 @@ class LocalBlockFn(torch.autograd.Function):
         cp, hlo = ctx.cp, ctx.hlo
         x = s1                                  # shape / dtype / device template of the [B, L, C] activations
         B, L, KS, dil, T1, T2, NJ = ctx.meta
+        bm1 = ctx.bm1                           # positions x 128 channels one LN1 partial counts
         dev = x.device
         stream = _lib.stream_ptr(dev)
         params = ctx.params
@@ -393,7 +452,7 @@ class LocalBlockFn(torch.autograd.Function):
         else:
             slab_args = dwl_slab(dev)
         _lib.call("pbx_ln2_linear_bwd", dh2t.data_ptr(), s2.data_ptr(), st2.data_ptr(), sums2.data_ptr(), TA,
-                  g2.data_ptr(), pre_l.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, BM1, g1.data_ptr(),
+                  g2.data_ptr(), pre_l.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, bm1, g1.data_ptr(),
                   be1.data_ptr(), wl_b.data_ptr(), consts.data_ptr(), dh1.data_ptr(), sums1.data_ptr(),
                   dg2.data_ptr(), dbe2.data_ptr(), dg1.data_ptr(), dbe1.data_ptr(), dwl.data_ptr(), dbl.data_ptr(),
                   dgb.data_ptr(), B, L, LN_EPS, *slab_args, det, int(not late_fold), 0, stream)
@@ -423,7 +482,7 @@ class LocalBlockFn(torch.autograd.Function):
         if not fin:
             # LN1 finalize (ds1) + gradient of the broadcast global->local vector
             ds1 = torch.empty_like(x)
-            _lib.call("pbx_ln1_finalize", dh1.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, BM1, sums1.data_ptr(),
+            _lib.call("pbx_ln1_finalize", dh1.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, bm1, sums1.data_ptr(),
                       TS1, g1.data_ptr(), ds1.data_ptr(), dgb.data_ptr(), B, L, LN_EPS, int(fused_deterministic()),
                       stream)
             if cp is not None:
@@ -431,7 +490,7 @@ class LocalBlockFn(torch.autograd.Function):
             dgb_ready()
         demb = None
         if fin:
-            conv_dgrad_fin(dh1, s1, st1, T1, BM1, sums1, TS1, g1, pre_n, pre_w, wtn, wtw, dx, dpn, dpw, dgb, B, L,
+            conv_dgrad_fin(dh1, s1, st1, T1, bm1, sums1, TS1, g1, pre_n, pre_w, wtn, wtw, dx, dpn, dpw, dgb, B, L,
                            KS, dil, stream)
             dgb_ready()
         elif ctx.emb_grad:
@@ -465,7 +524,7 @@ class LocalBlockFn(torch.autograd.Function):
             notify_grads_ready(direct)
         pgrads = [None if d else g for (g, d) in dsts]
         gemb = dE if demb is not None and not dE_direct else None
-        return (dx, dgb, *pgrads, None, None, None, None, None, None, gemb, None)
+        return (dx, dgb, *pgrads, None, None, None, None, None, None, gemb, None, None)
 
 
 def embed_tokens(tokens: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -532,11 +591,11 @@ def conv_images(wn: torch.Tensor, ww: torch.Tensor):
 
 
 def local_block(x: torch.Tensor, gb: torch.Tensor, blk, packed=None, tail: bool = False,
-                cp=None, tok=None, emb=None, emb_grad: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                cp=None, tok=None, emb=None, emb_grad: bool = False, tok_tab=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Run the fused local track of ``blk`` (a ``ProteinBERTBlock``); ``tail``: it is the first block;
     ``cp``: context-parallel shard (:class:`..parallel.cp_fused.CPShard`); ``tok`` / ``emb``: ``x`` is
     the token embedding bf16(emb[tok]); ``emb_grad``: the backward returns ``emb``'s gradient (``x``
-    from :func:`embed_tokens`, no autograd history)."""
+    from :func:`embed_tokens`, no autograd history); ``tok_tab``: this step's :func:`conv_tok_tables`."""
     att = blk.global_attention_layer
     wv = _wv_bf16(att)                                                       # [H*vd, C]
     nc = blk.local_narrow_conv_layer[0]
@@ -544,4 +603,4 @@ def local_block(x: torch.Tensor, gb: torch.Tensor, blk, packed=None, tail: bool 
     return LocalBlockFn.apply(x, gb, nc.weight, nc.bias, wc.weight, wc.bias, blk.local_norm_1.weight,
                               blk.local_norm_1.bias, blk.local_linear_layer[0].weight, blk.local_linear_layer[0].bias,
                               blk.local_norm_2.weight, blk.local_norm_2.bias, wv, blk.wide_conv_dilation, packed,
-                              tail, cp, tok, emb, emb_grad)
+                              tail, cp, tok, emb, emb_grad, tok_tab)
