@@ -50,7 +50,9 @@ def test_fused_adam_skip_flag():
 
 @pytest.mark.parametrize("n", [1, 7, 4096, 300001])
 def test_nonfinite_flag_kernel(n):
-    """pbx_nonfinite_flag: 1 iff any gradient element is NaN / Inf (every position, tail included)."""
+    """pbx_nonfinite_flag through FusedAdam: 1 iff any gradient element is NaN / Inf.  This is the arena-padded
+    path: the arena pads every segment to 64 elements, so n = 1 and n = 7 reach the kernel as 64 and its scalar
+    tail never runs here (test_hip_optim_flat.py::test_nonfinite_flag_direct calls the kernel with n itself)."""
     p = torch.nn.Parameter(torch.zeros(n, device="cuda"))
     fa = FusedAdam([p], lr=0.1)
     p.grad.copy_(torch.randn(n, device="cuda") * 1e30)          # huge but finite: not flagged
