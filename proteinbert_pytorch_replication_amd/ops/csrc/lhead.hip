@@ -1,5 +1,6 @@
-// Local (amino-acid) pretraining head + its loss, reference semantics, as coalesced multi-pass kernels
-// (SURVEY K9/K10).
+// Local (amino-acid) pretraining head + its loss, reference semantics: one launch up to
+// 2048 samples per GPU (lhead_onepass_kernel, below), coalesced multi-pass kernels above that and when a
+// data-parallel group shares the batch axis of the softmax.
 //
 // Reference: ProteinBERT/modules.py:277-284,304 (Linear C -> V, then nn.Softmax() with the implicit
 // dim, which for the [B, L, V] output is dim 0: a softmax over the BATCH for every (position, token))
@@ -13,11 +14,13 @@
 //   dh = dZ Wo ;  dWo = dZ^T h ;  dbo = sum dZ
 //
 // The batch coupling needs two statistics per (l, v) over all B samples before any gradient exists,
-// so the head runs as passes over row tiles of 16 samples x 32 positions (each sample's 32 rows are one
-// contiguous 8 KB run of h): (1) logits + per-tile (max, sum exp) partials, (2) fold them to (M, 1/S),
-// (3) CE loss + per-tile partials of G P, (4) fold them to T, (5) dZ, dh = dZ Wo (MFMA) and dZ rows for
-// the dWo GEMM.  A workgroup per POSITION walking all B samples (the round-2 form) read rows L * 256
-// bytes apart and ran at ~150 us for B = L = 512; every pass here streams contiguous rows.
+// so the multi-pass form runs as passes over row tiles of 16 samples x 32 positions (each sample's 32
+// rows are one contiguous 8 KB run of h): (1) logits + per-tile (max, sum exp) partials, (2) fold them to
+// (M, 1/S), (3) CE loss + per-tile partials of G P, (4) fold them to T, (5) dZ, dh = dZ Wo (MFMA) and dZ
+// rows for the dWo GEMM; every pass streams contiguous rows, but Z (fp32) is written once and read twice.
+// The one-launch form gives a workgroup one POSITION and all B samples: its rows are 256-B runs L * 256
+// bytes apart (the round-2 form of it, one tile in flight, ran at ~150 us for B = L = 512), which it reads
+// two tiles ahead per wave, and nothing but h, y, w, dh and dz crosses the memory bus.
 #include "mfma.h"
 
 using namespace pbx;
@@ -360,218 +363,257 @@ __global__ void __launch_bounds__(512) lhead_grad_kernel(const float* __restrict
   }
 }
 
-// ---- one-launch form (B <= 512): a workgroup owns PP = 2 positions and ALL samples, so both batch
-// reductions ((max, sum exp), then T = sum_b G P) are workgroup-local and the head is one pass over h:
-// (1) Z = h Wo^T + bo for the 2B rows (MFMA) into an fp32 LDS table, (2) column (max, sum exp) ->
-// (M, 1/S), (3) per row P, the CE term and G P (P kept in registers), (4) column sums -> T, (5) dZ =
-// P (G - T) into the table and the bf16 dz rows for the dWo GEMM, (6) dbo partial and dh = dZ Wo (MFMA,
-// staged through LDS for 256-B row stores).  h is read once (512-B runs per sample), Z never leaves
-// the CU.
-// PP = 1 (513 <= B <= 1024): a workgroup owns ONE position; the table holds PP * B <= 1024 rows either way.
-constexpr int ROWSF = 1024;       // table rows = PP * max B
-constexpr int ZS = VP + 1;        // fp32 row stride of the table (column walks hit distinct banks)
-constexpr int FUSED_LDS = ROWSF * ZS * 4 + VP * 256 + VP * 4 + 8 * 64 * 8 + 64 * 8 + 64 * 4 + 8 * 4;
+// ---- one-launch form (B <= 2048), the logits in REGISTERS (B <= 256 * TPW; TPW = 2, 4, 8).  A workgroup
+// owns one position and ALL samples, so both batch reductions ((max, sum exp), then T = sum_b G P) are
+// workgroup-local, the head is one pass over h and Z never leaves the CU.  Wave w owns the 32-sample row
+// tiles w, w + 8, ... (TPW of them) and keeps their logits transposed, in the MFMA accumulator layout of
+// Z^T = Wo h^T: lane (r, hh) holds sample r of each tile and the 16 tokens v = (e & 3) + 8 (e >> 2) + 4 hh,
+// so 2048 x 32 fp32 logits are 128 VGPRs per lane and never touch LDS.  (1) h tiles through a register ring RING tiles deep per wave (loads of tile
+// i + RING issued behind the MFMAs of tile i: 8 waves x RING x 8 KB in flight per CU), (2) per-wave
+// (max, sum exp) by lane butterflies, merged over the 8 waves -> (M, 1/S); E = exp(Z - m_wave) stays in
+// registers and P = E exp(m_wave - M) / S costs no second exp, (3) per sample the CE term and G P, summed
+// to T the same way, (4) per tile dZ = P (G - T) (exp(P) recomputed: keeping it would double the
+// registers), the bf16 dz rows, dh^T = Wo^T dZ^T (MFMA; K = v in the accumulator's own order, the Wo
+// fragment read with the matching row permutation), staged through the wave's LDS tile for 256-B row
+// stores that drain behind the next tile's math, (5) dbo partial.  No table, no atomics, no workspace.
+constexpr int OP_RING = 2;
+constexpr int OP_OTS = 272;      // staging row stride (256 B + 16): column writes / row reads at immediate offsets
+// two workgroups fit the 160 KiB of a CU (TPW = 2 leaves the registers for them)
+constexpr int OP_LDS = 8 * PT * OP_OTS + VP * 256 + VP * 4 + 8 * VP * 8 + VP * 8 + VP * 4 + 8 * 4;
+static_assert(2 * OP_LDS <= 160 * 1024, "two workgroups per CU");
 
-template <int PP>
-__global__ void __launch_bounds__(512) lhead_fused_kernel(const bf16_t* __restrict__ h, const float* __restrict__ wo,
-                                                          const float* __restrict__ bo,
-                                                          const long long* __restrict__ y,
-                                                          const float* __restrict__ wl, bf16_t* __restrict__ dh,
-                                                          bf16_t* __restrict__ dz, float* __restrict__ dbo_part,
-                                                          float* __restrict__ loss_part, int B, int L, int V,
-                                                          float inv_bl) {
+template <int TPW>
+__global__ void __launch_bounds__(512) lhead_onepass_kernel(const bf16_t* __restrict__ h, const float* __restrict__ wo,
+                                                            const float* __restrict__ bo,
+                                                            const long long* __restrict__ y,
+                                                            const float* __restrict__ wl, bf16_t* __restrict__ dh,
+                                                            bf16_t* __restrict__ dz, float* __restrict__ dbo_part,
+                                                            float* __restrict__ loss_part, int B, int L, int V,
+                                                            float inv_bl) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NPAIR = PP * 32, PARTS = 512 / NPAIR;   // (position, v) columns; sample slices per column
-  float* zt = reinterpret_cast<float*>(smem);                              // [PP * B][ZS]
-  unsigned char* wos = smem + ROWSF * ZS * 4;                              // [32][128] bf16
+  unsigned char* ot = smem;                                                // [8 waves][32][128] bf16: dh staging
+  unsigned char* wos = smem + 8 * PT * OP_OTS;                             // [32][128] bf16
   float* bo_s = reinterpret_cast<float*>(wos + VP * 256);                  // [32]
-  float2* red = reinterpret_cast<float2*>(bo_s + VP);                      // [PARTS][NPAIR]
-  float2* ms = red + 8 * 64;                                               // [NPAIR] (M, 1/S) per (p, v)
-  float* tt = reinterpret_cast<float*>(ms + 64);                           // [NPAIR] T per (p, v)
-  float* lred = tt + 64;                                                   // [8]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  float2* red = reinterpret_cast<float2*>(bo_s + VP);                      // [8][32] per-wave (max, sum exp)
+  float2* ms = red + 8 * VP;                                               // [32] (M, 1/S)
+  float* tred = reinterpret_cast<float*>(red);                             // [8][32] per-wave sum G P, then sum dZ
+  float* dbr = tred + 8 * VP;                                              //   (each behind a barrier after red's / tred's readers)
+  float* tt = reinterpret_cast<float*>(ms + VP);                           // [32] T
+  float* lred = tt + VP;                                                   // [8]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, hh = lane >> 5;
   const int q = tr_q(lane), tc = tr_c(lane);
-  const int l0 = blockIdx.x * PP;
-  const int NR = PP * B, NT = (NR + 31) / 32;
+  const int l = blockIdx.x;
+  const int NT = (B + 31) >> 5;
+  // (1) logits: Z^T tile = Wo h_tile^T
+  bf16x8 ring[OP_RING][8];
+  auto load_tile = [&](bf16x8 (&dst)[8], int t) {
+    const int s = min(t * 32 + r, B - 1);                                  // clamped: loads in bounds
+    const bf16_t* src = h + ((size_t)s * L + l) * CH + 8 * hh;
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) dst[kk] = *reinterpret_cast<const bf16x8*>(src + kk * 16);
+  };
+#pragma unroll
+  for (int i = 0; i < OP_RING && i < TPW; ++i)
+    if (w + 8 * i < NT) load_tile(ring[i], w + 8 * i);
   stage_wo(wos, bo_s, wo, bo, V);
   __syncthreads();
-  // (1) logits
+  float Z[TPW][16];
   {
     bf16x8 wf[8];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) wf[kk] = lds_frag(wos, swz256(r, kk * 2 + hh));
-    const float bv = bo_s[r];
-#pragma unroll 2
-    for (int t = w; t < NT; t += 8) {
-      const int row = min(t * 32 + r, NR - 1);
-      const int p = row / B, s = row - (row / B) * B;
-      const bf16_t* src = h + ((size_t)s * L + min(l0 + p, L - 1)) * CH + 8 * hh;
-      bf16x8 hf[8];
 #pragma unroll
-      for (int kk = 0; kk < 8; ++kk) hf[kk] = *reinterpret_cast<const bf16x8*>(src + kk * 16);
+    for (int i = 0; i < TPW; ++i) {
+      const int t = w + 8 * i;
       f32x16_t acc = zero16();
+      if (t < NT) {
 #pragma unroll
-      for (int kk = 0; kk < 8; ++kk) acc = mfma32(hf[kk], wf[kk], acc);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int rr = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        if (rr < NR) zt[rr * ZS + r] = acc[e] + bv;
+        for (int kk = 0; kk < 8; ++kk) acc = mfma32(wf[kk], ring[i % OP_RING][kk], acc);
+        if (i + OP_RING < TPW && t + 8 * OP_RING < NT) load_tile(ring[i % OP_RING], t + 8 * OP_RING);
       }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) Z[i][e] = acc[e];
     }
   }
-  __syncthreads();
-  const int pair = tid % NPAIR, part = tid / NPAIR;  // column (p, v) and sample slice of the reductions
-  const int pp = pair >> 5, pv = pair & 31;
-  // (2) (max, sum exp) over the samples of every (p, v)
+  // (2) (max, sum exp) over the samples of every token: in-lane over the tiles, butterfly over the 32
+  // samples of a tile row, then over the waves
+  float m[16], f[16];
   {
-    float m = -3.0e38f, se = 0.f;
-    for (int s = part; s < B; s += PARTS) {
-      const float z = zt[(pp * B + s) * ZS + pv];
-      const float mn = fmaxf(m, z);
-      se = se * __expf(m - mn) + __expf(z - mn);
-      m = mn;
+    const float4* bp = reinterpret_cast<const float4*>(bo_s + 4 * hh);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 b4 = bp[2 * g];
+      f[4 * g] = b4.x; f[4 * g + 1] = b4.y; f[4 * g + 2] = b4.z; f[4 * g + 3] = b4.w;
     }
-    red[part * NPAIR + pair] = make_float2(m, se);
+  }
+#pragma unroll
+  for (int e = 0; e < 16; ++e) m[e] = -3.0e38f;
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    const bool ok = (w + 8 * i) * 32 + r < B;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      Z[i][e] = ok ? Z[i][e] + f[e] : -3.0e38f;
+      m[e] = fmaxf(m[e], Z[i][e]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) m[e] = fmaxf(m[e], __shfl_xor(m[e], o, 64));
+  }
+#pragma unroll
+  for (int e = 0; e < 16; ++e) f[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    const bool ok = (w + 8 * i) * 32 + r < B;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      Z[i][e] = ok ? __expf(Z[i][e] - m[e]) : 0.f;
+      f[e] += Z[i][e];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) f[e] += __shfl_xor(f[e], o, 64);
+  }
+  if (r == 0) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) red[w * VP + (e & 3) + 8 * (e >> 2) + 4 * hh] = make_float2(m[e], f[e]);
+  }
+  // labels and weights of this lane's samples (clamped addresses, loaded unconditionally: in flight
+  // behind the merge over the waves)
+  int yv[TPW];
+  float wg[TPW];
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    const int s = (w + 8 * i) * 32 + r;
+    const size_t gi = (size_t)min(s, B - 1) * L + l;
+    const long long yr = y[gi];
+    const float wr = wl[gi];
+    yv[i] = s < B ? (int)yr : -1;
+    wg[i] = s < B ? wr : 0.f;
   }
   __syncthreads();
-  if (tid < NPAIR) {
+  if (tid < VP) {
     float mm = red[tid].x;
 #pragma unroll
-    for (int k = 1; k < PARTS; ++k) mm = fmaxf(mm, red[k * NPAIR + tid].x);
+    for (int k = 1; k < 8; ++k) mm = fmaxf(mm, red[k * VP + tid].x);
     float ss = 0.f;
 #pragma unroll
-    for (int k = 0; k < PARTS; ++k) ss += red[k * NPAIR + tid].y * __expf(red[k * NPAIR + tid].x - mm);
-    ms[tid] = make_float2(mm, ss > 0.f ? 1.0f / ss : 0.f);
+    for (int k = 0; k < 8; ++k) ss += red[k * VP + tid].y * __expf(red[k * VP + tid].x - mm);
+    ms[tid] = make_float2(mm, tid < V && ss > 0.f ? 1.0f / ss : 0.f);
   }
   __syncthreads();
-  // (3) per row: P (registers), CE term, G P into the table
-  constexpr int RPT = ROWSF / 512;                  // rows per thread
-  float P[RPT][VP], rse[RPT], coef[RPT];
-  int yv[RPT];
-  float lsum = 0.f;
+  // P = E exp(m_wave - M) / S (0 for v >= V and for rows past B)
 #pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int row = tid + 512 * k;
-    // rows past NR (small B) give p = row / B up to 1023 / B: clamp the ms[] index into the PP positions
-    const int p = min(row / B, PP - 1), s = row - (row / B) * B;
-    const bool ok = row < NR && l0 + p < L;
-    const size_t gi = (size_t)s * L + min(l0 + p, L - 1);
-    yv[k] = ok ? (int)y[gi] : -1;
-    const float wgt = ok ? wl[gi] : 0.f;
-    coef[k] = wgt * inv_bl;
-    float e[VP], se = 0.f, py = 0.f;
+  for (int e = 0; e < 16; ++e) {
+    const float2 mv = ms[(e & 3) + 8 * (e >> 2) + 4 * hh];
+    f[e] = __expf(m[e] - mv.x) * mv.y;
+  }
 #pragma unroll
-    for (int v = 0; v < VP; ++v) {
-      const float2 mv = ms[p * 32 + v];
-      const float z = row < NR ? zt[row * ZS + v] : 0.f;
-      P[k][v] = ok && v < V ? __expf(z - mv.x) * mv.y : 0.f;
-      e[v] = ok && v < V ? __expf(P[k][v]) : 0.f;
-      se += e[v];
-      py += v == yv[k] ? P[k][v] : 0.f;
+  for (int i = 0; i < TPW; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) Z[i][e] *= f[e];
+  // (3) per sample: CE term and G P
+  float lse[TPW], lsum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) f[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    float ex[16], se = 0.f, py = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int v = (e & 3) + 8 * (e >> 2) + 4 * hh;
+      ex[e] = v < V ? __expf(Z[i][e]) : 0.f;
+      se += ex[e];
+      py += v == yv[i] ? Z[i][e] : 0.f;
     }
-    rse[k] = se > 0.f ? 1.0f / se : 0.f;
-    lsum += ok ? wgt * (__logf(se) - py) : 0.f;
-    if (row < NR) {
+    se += __shfl_xor(se, 32, 64);
+    const float rse = 1.0f / se;                       // se >= V: exp(P) >= 1 for every v < V
+    lse[i] = __logf(se);
+    const float coef = wg[i] * inv_bl;
+    lsum += wg[i] * ((hh == 0 ? lse[i] : 0.f) - py);
 #pragma unroll
-      for (int v = 0; v < VP; ++v) zt[row * ZS + v] = coef[k] * (e[v] * rse[k] - (v == yv[k] ? 1.f : 0.f)) * P[k][v];
+    for (int e = 0; e < 16; ++e) {
+      const int v = (e & 3) + 8 * (e >> 2) + 4 * hh;
+      f[e] += coef * (ex[e] * rse - (v == yv[i] ? 1.f : 0.f)) * Z[i][e];
     }
   }
-  __syncthreads();
-  // (4) T = sum_b G P for every (p, v)
-  {
-    float a = 0.f;
-    for (int s = part; s < B; s += PARTS) a += zt[(pp * B + s) * ZS + pv];
-    red[part * NPAIR + pair] = make_float2(a, 0.f);
-  }
-  __syncthreads();
-  if (tid < NPAIR) {
-    float a = 0.f;
 #pragma unroll
-    for (int k = 0; k < PARTS; ++k) a += red[k * NPAIR + tid].x;
-    tt[tid] = a;
-  }
-  __syncthreads();
-  // (5) dZ = P (G - T): fp32 into the table, bf16 rows for the dWo GEMM
+  for (int e = 0; e < 16; ++e) {
 #pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int row = tid + 512 * k;
-    if (row >= NR) continue;
-    const int p = row / B, s = row - (row / B) * B;
-    const bool ok = l0 + p < L;
-    float d[VP];
-#pragma unroll
-    for (int v = 0; v < VP; ++v) {
-      const float G = coef[k] * (__expf(P[k][v]) * rse[k] - (v == yv[k] ? 1.f : 0.f));
-      d[v] = ok && v < V ? P[k][v] * (G - tt[p * 32 + v]) : 0.f;
-      zt[row * ZS + v] = d[v];
-    }
-    if (ok) {
-      uint4* dst = reinterpret_cast<uint4*>(dz + ((size_t)s * L + l0 + p) * VP);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) dst[c] = packq8(d + 8 * c);
-    }
+    for (int o = 1; o < 32; o <<= 1) f[e] += __shfl_xor(f[e], o, 64);
   }
   lsum = wave_reduce_sum(lsum);
+  if (r == 0) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) tred[w * VP + (e & 3) + 8 * (e >> 2) + 4 * hh] = f[e];
+  }
   if (lane == 0) lred[w] = lsum;
   __syncthreads();
+  if (tid < VP) {
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a += tred[k * VP + tid];
+    tt[tid] = a;
+  }
   if (tid == 0) {
     float a = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) a += lred[k];
-    loss_part[blockIdx.x] = a * inv_bl;
+    loss_part[l] = a * inv_bl;
   }
-  // (6a) dbo partial: column sums of dZ (16 row slices of the 32 columns)
-  {
-    const int v = tid & 31, sl = tid >> 5;
-    float a = 0.f;
-    for (int row = sl; row < NR; row += 16) a += zt[row * ZS + v];
-    reinterpret_cast<float*>(red)[sl * 32 + v] = a;
+  __syncthreads();
+  // (4) per tile: dZ = P (G - T), dz rows, dh^T = Wo^T dZ^T, 256-B row stores
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    m[e] = tt[(e & 3) + 8 * (e >> 2) + 4 * hh];
+    f[e] = 0.f;
   }
-  // (6b) dh = dZ Wo: A fragments (bf16 of the fp32 table) of this wave's row tiles first
-  constexpr int TPW = ROWSF / 32 / 8;               // row tiles per wave
-  bf16x8 fa[TPW][2];
-#pragma unroll
-  for (int i = 0; i < TPW; ++i) {
-    const int row = (w + 8 * i) * 32 + r;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      float a8[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a8[j] = row < NR ? zt[row * ZS + kk * 16 + 8 * hh + j] : 0.f;
-      fa[i][kk] = pack8(a8);
-    }
-  }
-  __syncthreads();                                   // table and dbo slices read
-  if (tid < V) {
-    float a = 0.f;
-#pragma unroll
-    for (int sl = 0; sl < 16; ++sl) a += reinterpret_cast<float*>(red)[sl * 32 + tid];
-    dbo_part[(size_t)blockIdx.x * V + tid] = a;
-  }
-  unsigned char* myot = smem + w * PT * 256;        // per-wave [32][128] bf16 staging over the table
+  unsigned char* myot = ot + w * PT * OP_OTS;
 #pragma unroll
   for (int i = 0; i < TPW; ++i) {
     const int t = w + 8 * i;
     if (t >= NT) break;
-    f32x16_t acc[4];
+    const int s = t * 32 + r;
+    const float coef = wg[i] * inv_bl;
+    const int yl = yv[i] - 4 * hh;                     // the label among this lane's tokens
+    float d[16];
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) acc[ct] = zero16();
+    for (int e = 0; e < 16; ++e) {
+      const float ge = coef * __expf(Z[i][e] - lse[i]);                    // coef exp(P) / se
+      const float G = (e & 3) + 8 * (e >> 2) == yl ? ge - coef : ge;
+      d[e] = Z[i][e] * (G - m[e]);
+      f[e] += d[e];
+    }
+    if (s < B) {
+      bf16_t* dst = dz + ((size_t)s * L + l) * VP + 4 * hh;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int rlo = kk * 16 + 8 * hh + q;
+      for (int g = 0; g < 4; ++g) *reinterpret_cast<uint2*>(dst + 8 * g) = packq4(d + 4 * g);
+    }
+    // A = Wo^T (row = channel, K = v): lane K slots 8 hh + j <-> v = 16 kk + 4 hh + j (j < 4),
+    // 16 kk + 8 + 4 hh + j - 4 (j >= 4), the tokens of this lane's d[8 kk + j]
+    const bf16x8 fa[2] = {pack8(d), pack8(d + 8)};
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int col = ct * 32 + tc;
-        const bf16x8 fb = cat_tr(lds_tr(wos, swz256e(rlo, col)), lds_tr(wos, swz256e(rlo + 4, col)));
-        acc[ct] = mfma32(fa[i][kk], fb, acc[ct]);
+    for (int ct = 0; ct < 4; ++ct) {
+      f32x16_t acc = zero16();
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int rlo = kk * 16 + 4 * hh + q, col = ct * 32 + tc;
+        const bf16x8 fb = cat_tr(lds_tr(wos, swz256e(rlo, col)), lds_tr(wos, swz256e(rlo + 8, col)));
+        acc = mfma32(fb, fa[kk], acc);
+      }
+      // D[channel ct * 32 + (e & 3) + 8 (e >> 2) + 4 hh][sample r]: 4 consecutive channels per register quad
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float o4[4] = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+        *reinterpret_cast<uint2*>(myot + r * OP_OTS + 8 * hh + (ct * 4 + g) * 16) = packq4(o4);
       }
     }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int e = 0; e < 16; ++e)
-        *reinterpret_cast<bf16_t*>(myot + swz256e((e & 3) + 8 * (e >> 2) + 4 * hh, ct * 32 + r)) = f2bf(acc[ct][e]);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -579,15 +621,31 @@ __global__ void __launch_bounds__(512) lhead_fused_kernel(const bf16_t* __restri
     for (int k = 0; k < 8; ++k) {
       const int idx = lane + 64 * k;                 // 512 16-B chunks = 32 rows x 16
       const int rr = idx >> 4, c8 = idx & 15;
-      const int row = t * 32 + rr;
-      const int p = row / B, s = row - (row / B) * B;
-      if (row < NR && l0 + p < L)
-        *reinterpret_cast<uint4*>(dh + ((size_t)s * L + l0 + p) * CH + c8 * 8) =
-            *reinterpret_cast<const uint4*>(myot + swz256(rr, c8));
+      const int sr = t * 32 + rr;
+      if (sr < B)
+        *reinterpret_cast<uint4*>(dh + ((size_t)sr * L + l) * CH + c8 * 8) =
+            *reinterpret_cast<const uint4*>(myot + rr * OP_OTS + c8 * 16);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  // (5) dbo partial
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) f[e] += __shfl_xor(f[e], o, 64);
+  }
+  if (r == 0) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dbr[w * VP + (e & 3) + 8 * (e >> 2) + 4 * hh] = f[e];
+  }
+  __syncthreads();
+  if (tid < V) {
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a += dbr[k * VP + tid];
+    dbo_part[(size_t)l * V + tid] = a;
   }
 }
 }  // namespace
@@ -662,25 +720,28 @@ PBX_EXPORT int pbx_local_head3(const void* h, const float* wo, const float* bo, 
   return rc;
 }
 
-// Positions per workgroup of pbx_local_head_fused: 2 for B <= 512, 1 for B <= 1024 (0: unsupported).
-PBX_EXPORT int pbx_local_head_fused_pp(int B) { return B <= 512 ? 2 : B <= 1024 ? 1 : 0; }
+// Positions per workgroup of pbx_local_head_fused: 1 for B <= 2048 (0: unsupported, the caller takes the
+// five-pass form).  Sizes its outputs: dbo_part [ceil(L / pp)][V], loss_part [ceil(L / pp)].
+PBX_EXPORT int pbx_local_head_fused_pp(int B) { return B >= 1 && B <= 2048 ? 1 : 0; }
 
-// One-launch head (B <= 1024): dbo_part [ceil(L / pp)][V], loss_part [ceil(L / pp)] (each already / (B L)),
-// pp = pbx_local_head_fused_pp(B)
+// One-launch head (B <= 2048): dbo_part [L][V], loss_part [L] (each already / (B L)).  The kernel is
+// instantiated for 2, 4 and 8 row tiles per wave (B <= 512, 1024, 2048): fewer logits registers leave room
+// for a second workgroup per CU at the smaller batches.
 PBX_EXPORT int pbx_local_head_fused(const void* h, const float* wo, const float* bo, const void* y, const float* wl,
                                     void* dh, void* dz, float* dbo_part, float* loss_part, int B, int L, int V,
                                     hipStream_t st) {
-  const int pp = pbx_local_head_fused_pp(B);
-  if (V > VP || V < 1 || B < 1 || pp == 0 || L < 1) return (int)hipErrorInvalidValue;
+  if (V > VP || V < 1 || pbx_local_head_fused_pp(B) == 0 || L < 1) return (int)hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)lhead_fused_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS);
-    (void)hipFuncSetAttribute((const void*)lhead_fused_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS);
+    (void)hipFuncSetAttribute((const void*)lhead_onepass_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, OP_LDS);
+    (void)hipFuncSetAttribute((const void*)lhead_onepass_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, OP_LDS);
+    (void)hipFuncSetAttribute((const void*)lhead_onepass_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, OP_LDS);
     attr = true;
   }
   const float inv_bl = 1.0f / ((float)B * (float)L);
-  hipLaunchKernelGGL(pp == 2 ? lhead_fused_kernel<2> : lhead_fused_kernel<1>, dim3((L + pp - 1) / pp), dim3(512),
-                     FUSED_LDS, st, (const bf16_t*)h, wo, bo, (const long long*)y, wl, (bf16_t*)dh, (bf16_t*)dz,
-                     dbo_part, loss_part, B, L, V, inv_bl);
+  auto k = B <= 512 ? lhead_onepass_kernel<2> : B <= 1024 ? lhead_onepass_kernel<4> : lhead_onepass_kernel<8>;
+  hipLaunchKernelGGL(k, dim3(L), dim3(512), OP_LDS, st, (const bf16_t*)h, wo, bo, (const long long*)y, wl,
+                     (bf16_t*)dh, (bf16_t*)dz, dbo_part, loss_part, B, L, V, inv_bl);
   return pbx_launch_status();
 }
+

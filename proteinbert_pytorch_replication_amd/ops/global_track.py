@@ -38,27 +38,32 @@ _lib.register("pbx_local_head_fused", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _
 _lib.register("pbx_local_head3_a", [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P])
 _lib.register("pbx_local_head3_b", [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
 _lib.register("pbx_local_head3_c", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-# local head: one launch for B <= 512 (pbx_local_head_fused: 61 vs 108 us for the five-pass form at
-# B = L = 512, profiles/r3k_*); larger per-GPU batches take the five-pass form
+# local head: one launch (pbx_local_head_fused) up to LHEAD_FUSED_MAX_B samples per GPU -- 48 / 86 / 165 us
+# against 100 / 197 / 387 us for the five-pass form at B = 512 / 1024 / 2048, L = 512
+# (profiles/r10/lhead_onepass_ubench.txt); larger per-GPU batches, and any the kernel does not support
+# (pbx_local_head_fused_pp(B) == 0), take the five-pass form.  LHEAD_FUSED_MAX_B = 1024 routes 1025..2048 to
+# the five-pass form as before round 10 (the A/B switch of tools/ubench/lhead_b.py).
 LHEAD_FUSED = True
+LHEAD_FUSED_MAX_B = 2048
 
 
 def local_head_forward(h: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, y_l: torch.Tensor, w_l: torch.Tensor,
                        loss_slot: torch.Tensor):
     """Local head + its CE term, reference semantics (softmax over the batch axis; ``csrc/lhead.hip``):
-    five coalesced passes over 16-sample x 32-position row tiles.  Writes the mean loss into ``loss_slot``
-    and returns (dh [B, L, 128] bf16, dz [B*L, 32] bf16 -- dL/dlogits for the dWo GEMM -- and the
-    per-tile bias-gradient partials [tiles, V])."""
+    one launch with a workgroup per position x all samples up to ``LHEAD_FUSED_MAX_B`` samples, five
+    coalesced passes over 16-sample x 32-position row tiles above.  Writes the mean loss into
+    ``loss_slot`` and returns (dh [B, L, 128] bf16, dz [B*L, 32] bf16 -- dL/dlogits for the dWo GEMM --
+    and the per-workgroup bias-gradient partials [tiles, V])."""
     dev = h.device
     st = _s(dev)
     B, L, C = h.shape
     V = wo.shape[0]
     if batch_softmax.active():
         return _local_head_dp(h, wo, bo, y_l, w_l, loss_slot)
-    if LHEAD_FUSED and B <= 1024:
-        # one launch: a workgroup per 2 positions (B <= 512) or 1 (B <= 1024) x all samples (the batch
-        # reductions stay on chip)
-        pp = _lib.lib().pbx_local_head_fused_pp(B)
+    pp = _lib.lib().pbx_local_head_fused_pp(B) if LHEAD_FUSED and B <= LHEAD_FUSED_MAX_B else 0
+    if pp:
+        # one launch: a workgroup per position x all samples (the batch reductions stay on chip; no Z /
+        # partials workspace, and the loss fold runs over L rows)
         nt = (L + pp - 1) // pp
         dh = torch.empty_like(h)
         dz = torch.empty((B * L, 32), dtype=BF16, device=dev)
