@@ -8,12 +8,14 @@ missing library is an error, never a silent fallback to eager ops.
 from __future__ import annotations
 
 import ctypes
+import glob
 import os
-from typing import Optional
+import re
+from typing import Dict, Optional
 
 import torch
 
-from .build import HIP_LIB as _BUILT_HIP_LIB, HIP_LIB_EXACT as _BUILT_HIP_LIB_EXACT, HOST_LIB
+from .build import CSRC, HIP_LIB as _BUILT_HIP_LIB, HIP_LIB_EXACT as _BUILT_HIP_LIB_EXACT, HOST_LIB
 
 GELU_MODES = ("fitted", "exact")
 
@@ -49,42 +51,71 @@ def set_gelu(mode: str) -> None:
     HIP_LIB = want
     os.environ["PBX_GELU"] = mode     # child processes (DP ranks spawned later) inherit the choice
 
-_P = ctypes.c_void_p
-_I64 = ctypes.c_int64
-_I32 = ctypes.c_int
-_F32 = ctypes.c_float
-
-# name -> argtypes (all return int hipError_t)
-_SIGS = {
-    "pbx_adam_flat": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _P],
-    "pbx_sumsq_flat": [_P, _I64, _P, _P, _P],
-    "pbx_clip_scale_flat": [_P, _I64, _P, _F32, _P],
-    "pbx_nonfinite_flag": [_P, _I64, _P, _P, _F32, _I32, _P],
-    "pbx_fill_flat": [_P, _I64, _F32, _P],
-    "pbx_add_scalar": [_P, _F32, _P],
-    "pbx_add_i64": [_P, _I64, _P],
-    "pbx_colsum_set": [_P, _I32, _I32, _P, _P, _P],
-}
-
-_lib: Optional[ctypes.CDLL] = None
-_host: Optional[ctypes.CDLL] = None
-
 
 class HipError(RuntimeError):
     pass
 
 
+# The C prototypes are the ABI: every ``PBX_EXPORT int name(params)`` of csrc/*.hip is a launcher, and its
+# ctypes signature is derived from the declared parameter types (adding a launcher needs no Python declaration).
+_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong,
+           "unsigned long long": ctypes.c_ulonglong, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
+_TYPE_WORDS = {w for t in _CTYPES for w in t.split()} | {"signed", "short", "char", "double", "void"}
+_COMMENT = re.compile(r"//[^\n]*|/\*.*?\*/", re.S)
+_PROTO = re.compile(r"\bPBX_EXPORT\b([^(;{}]*)\(([^)]*)\)\s*(.)", re.S)
+
+
+def parse_launchers(text: str, where: str) -> Dict[str, list]:
+    """name -> ctypes argtypes of every ``PBX_EXPORT int name(params)`` in one source text.  A pointer or a
+    ``hipStream_t`` is a ``c_void_p``; any other type outside ``_CTYPES`` is an error naming the function,
+    never a guess: an unsupported prototype fails at import on the CPU, not as a bad call on the GPU."""
+    text = _COMMENT.sub(" ", text)
+    table: Dict[str, list] = {}
+    for m in _PROTO.finditer(text):
+        head, params, after = m.group(1).split(), m.group(2), m.group(3)
+        name = head[-1] if head else "?"
+        err = f"{where}: PBX_EXPORT {name}: "
+        if head[:-1] != ["int"]:
+            raise HipError(err + f"return type {' '.join(head[:-1])!r}: launchers return int (hipError_t)")
+        if "(" in params or after not in "{;":
+            raise HipError(err + "parentheses in the parameter list (function pointers, macros) are not supported")
+        args = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            words = [w for w in p.split() if w not in ("const", "__restrict__")]
+            if "*" in p or "hipStream_t" in words:
+                args.append(ctypes.c_void_p)
+                continue
+            ctype = _CTYPES.get(" ".join(words[:-1]))      # the last word is the parameter's name
+            if ctype is None or words[-1] in _TYPE_WORDS:
+                raise HipError(err + f"parameter {' '.join(p.split())!r}: unsupported type")
+            args.append(ctype)
+        table[name] = args
+    if len(table) != len(re.findall(r"\bPBX_EXPORT\b", text)):
+        raise HipError(f"{where}: a PBX_EXPORT use is not of the form `PBX_EXPORT int name(params)`")
+    return table
+
+
+_TABLE: Optional[Dict[str, list]] = None
+
+
+def launchers() -> Dict[str, list]:
+    """The launcher table of ``csrc/*.hip``, parsed at the first ``lib()`` or ``call()``."""
+    global _TABLE
+    if _TABLE is None:
+        table: Dict[str, list] = {}
+        for f in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+            with open(f) as fh:
+                table.update(parse_launchers(fh.read(), os.path.basename(f)))
+        _TABLE = table
+    return _TABLE
+
+
+_lib: Optional[ctypes.CDLL] = None
+_host: Optional[ctypes.CDLL] = None
+
+
 def available() -> bool:
     return os.path.exists(HIP_LIB)
-
-
-def register(name: str, argtypes) -> None:
-    """Kernel modules declare their launchers here (before first use)."""
-    _SIGS[name] = argtypes
-    if _lib is not None:
-        fn = getattr(_lib, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, ctypes.c_int
 
 
 def lib() -> ctypes.CDLL:
@@ -95,7 +126,7 @@ def lib() -> ctypes.CDLL:
                            f"Run `python -m proteinbert_pytorch_replication_amd.ops.build`.")
         _ = torch.cuda.is_available()  # make sure torch's HIP runtime is loaded first
         _lib = ctypes.CDLL(HIP_LIB, mode=ctypes.RTLD_LOCAL)
-        for name, args in _SIGS.items():
+        for name, args in launchers().items():
             fn = getattr(_lib, name, None)
             if fn is None:       # an older A/B build (PBX_HIP_LIB) without this launcher: call() raises
                 continue
@@ -130,8 +161,8 @@ _FN = {}
 def call(name: str, *args) -> None:
     fn = _FN.get(name)
     if fn is None:
-        if name not in _SIGS:   # ctypes would pass Python ints as 32-bit C ints and truncate device pointers
-            raise HipError(f"{name}: launcher not registered (import the ops module that declares it)")
+        if name not in launchers():   # untyped, ctypes would pass Python ints as 32-bit C ints and truncate pointers
+            raise HipError(f"{name}: no PBX_EXPORT launcher of that name in {CSRC}")
         fn = getattr(lib(), name, None)
         if fn is None:
             raise HipError(f"{name}: not exported by {HIP_LIB}")

@@ -7,17 +7,12 @@ zero-copy ``[B, A]`` broadcast of a per-sample ``[B]`` weight.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import torch
 
 from . import _lib
 from ..data.vocab import VOCAB_SIZE
-
-_P, _I, _F, _U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-_lib.register("pbx_synth_batch", [_P, _P, _I, _I, _I, _I, _I, _F, _I, _U64, _U64, _P, _P])
-_lib.register("pbx_corrupt_batch", [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _U64, _U64, _P, _P])
 
 
 def _check(t: torch.Tensor, dtype, name: str):
@@ -55,9 +50,6 @@ def corrupt_batch(tokens: torch.Tensor, ann: torch.Tensor, params, seed: int, st
     return ({"local": x_local, "global": x_global},
             {"local": tokens, "global": ann},
             {"local": w_local, "global": w_sample.unsqueeze(1).expand(B, A)})
-
-
-_lib.register("pbx_unpack_batch", [_P, _P, _P, _P, _I, _I, _I, _I, _P])
 
 
 def unpack_batch(tok_u8: torch.Tensor, bits: torch.Tensor, A: int) -> Tuple[torch.Tensor, torch.Tensor]:

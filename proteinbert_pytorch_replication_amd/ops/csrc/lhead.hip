@@ -78,7 +78,6 @@ __global__ void __launch_bounds__(512) lhead_logits_kernel(const bf16_t* __restr
   for (int si = 0; si < 2; ++si) {
     const int sl = 2 * w + si, b = b0 + sl;
     const int pos = p0 + r;
-    const bool okrow = b < B && pos < L;
     const size_t row = (size_t)min(b, B - 1) * L + min(pos, L - 1);        // clamped: loads in bounds
     bf16x8 hf[8];
 #pragma unroll
@@ -95,7 +94,6 @@ __global__ void __launch_bounds__(512) lhead_logits_kernel(const bf16_t* __restr
       zt[sl][pl][r] = z;
       if (b < B && pp < L) Z[((size_t)b * L + pp) * VP + r] = r < V ? z : 0.f;
     }
-    (void)okrow;
   }
   __syncthreads();
   // (max, sum exp) over the tile's valid samples for each (position, v): thread -> (pl, v pair)
@@ -650,7 +648,7 @@ __global__ void __launch_bounds__(512) lhead_onepass_kernel(const bf16_t* __rest
 }
 }  // namespace
 
-// Workspace sizes (floats) for pbx_local_head3: Z [B*L*32], part/tpart [ceil(B/16) * L * 32 * 2] each,
+// Workspace sizes (floats) for pbx_local_head3_a/_b/_c: Z [B*L*32], part/tpart [ceil(B/16) * L * 32 * 2] each,
 // MS/T [L * 32 * 2] each, loss_part / dbo_part [ntiles], [ntiles * V]; ntiles = ceil(B/16) ceil(L/32).
 PBX_EXPORT int pbx_local_head3_tiles(int B, int L) { return ((B + SB - 1) / SB) * ((L + PT - 1) / PT); }
 
@@ -670,7 +668,8 @@ void lhead3_attrs() {
 // The five passes in three stages, so that a data-parallel group can share the batch axis of the softmax
 // (parallel/batch_softmax.py): stage A = passes 1-2 -- with raw = 1 the fold leaves (M, S) for the caller
 // to merge over ranks into (M, 1/S) --, stage B = passes 3-4 (T, which the caller sums over ranks),
-// stage C = pass 5.
+// stage C = pass 5.  Outputs: dh [B][L][128] bf16, dz [B*L][32] bf16 (for dWo = dz^T h, a GEMM the caller
+// issues), dbo_part [ntiles][V], loss_part [ntiles] (each already divided by B L).
 PBX_EXPORT int pbx_local_head3_a(const void* h, const float* wo, const float* bo, float* Z, float* part, float* MS,
                                  int raw, int B, int L, int V, hipStream_t st) {
   if (V > VP || V < 1 || B < 1 || L < 1) return (int)hipErrorInvalidValue;
@@ -707,17 +706,6 @@ PBX_EXPORT int pbx_local_head3_c(const float* Z, const float* MS, const float* T
   hipLaunchKernelGGL(lhead_grad_kernel, dim3(nt), dim3(512), LDS5, st, Z, (const float2*)MS, (const float2*)T,
                      (const long long*)y, wl, wo, bo, (bf16_t*)dh, (bf16_t*)dz, dbo_part, B, L, V, inv_bl);
   return pbx_launch_status();
-}
-
-// Passes 1-5 (see header).  Outputs: dh [B][L][128] bf16, dz [B*L][32] bf16 (for dWo = dz^T h, a GEMM
-// the caller issues), dbo_part [ntiles][V], loss_part [ntiles] (each already divided by B L).
-PBX_EXPORT int pbx_local_head3(const void* h, const float* wo, const float* bo, const void* y, const float* wl,
-                               void* dh, void* dz, float* dbo_part, float* loss_part, float* Z, float* part,
-                               float* tpart, float* MS, float* T, int B, int L, int V, hipStream_t st) {
-  int rc = pbx_local_head3_a(h, wo, bo, Z, part, MS, 0, B, L, V, st);
-  if (rc == 0) rc = pbx_local_head3_b(Z, MS, y, wl, tpart, loss_part, T, B, L, V, st);
-  if (rc == 0) rc = pbx_local_head3_c(Z, MS, T, y, wl, wo, bo, dh, dz, dbo_part, B, L, V, st);
-  return rc;
 }
 
 // Positions per workgroup of pbx_local_head_fused: 1 for B <= 2048 (0: unsupported, the caller takes the

@@ -17,7 +17,6 @@ and cannot overflow.  No autograd Function is involved and nothing is kept for a
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Tuple
 
 import torch
@@ -26,15 +25,6 @@ from . import _lib, streams
 from .gemm import go_head_parts
 from .global_track import bf16_of
 from ..parallel import batch_softmax
-
-_P, _I, _F, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-_lib.register("pbx_local_head3_a", [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P])
-_lib.register("pbx_local_head3_tiles", [_I, _I])
-_lib.register("pbx_local_head_eval", [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_phead_eval_parts", [_L])
-_lib.register("pbx_phead_eval", [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P])
-_lib.register("pbx_go_head_eval", [_P, _L, _P, _L, _P, _P, _L, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_eval_fold", [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P])
 
 F32 = torch.float32
 NBIN = 256                      # histogram bins of the GO probability per class

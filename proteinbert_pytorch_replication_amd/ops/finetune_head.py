@@ -10,16 +10,9 @@ the input gradient (unfrozen encoders only) is fp32.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
-from . import global_track  # noqa: F401  (registers pbx_colsum_add)
-
-_P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-_lib.register("pbx_token_head_wgrad", [_P, _P, _P, _L, _I, _I, _P])
-_lib.register("pbx_token_head_fwd", [_P, _P, _P, _P, _L, _I, _P])
 
 
 def supported(h: torch.Tensor, n_classes: int) -> bool:

@@ -18,11 +18,6 @@ import torch
 
 from . import _lib
 
-_P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-_lib.register("pbx_gemm", [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_gemm_reduce", [_P, _I, _P, _L, _I, _I, _I, _P])
-_lib.register("pbx_go_head_fused", [_P, _L, _P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _P, _I, _I, _I, _P])
-
 BT = 128
 BK = 128
 
@@ -73,11 +68,6 @@ def gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, ta: bool = False, 
               N, M, N, K, s, 0, pad, st)
     _lib.call("pbx_gemm_reduce", slab.data_ptr(), s, out.data_ptr(), out.stride(0), M, N, int(accumulate), st)
     return out
-
-
-_lib.register("pbx_gemm_batch", [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p])
 
 
 def gemm_batch(problems, ta: bool, tb: bool, accumulate: bool = True) -> None:

@@ -25,19 +25,6 @@ from ..parallel import batch_softmax
 from ..train.arena import notify_grads_ready
 from ..utils.determinism import fused_deterministic
 
-_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_lib.register("pbx_row_ln_fwd", [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P])
-_lib.register("pbx_row_ln_bwd", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P])
-_lib.register("pbx_bias_gelu", [_P, _P, _P, _P, _I, _I, _P])
-_lib.register("pbx_bias_gelu_bwd", [_P, _P, _P, _P, _P, _I, _I, _P, _P])
-_lib.register("pbx_colsum_add", [_P, _I, _I, _P, _P, _P])
-_lib.register("pbx_colsum_set", [_P, _I, _I, _P, _P, _P])
-_lib.register("pbx_local_head3", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_local_head3_tiles", [_I, _I])
-_lib.register("pbx_local_head_fused", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_local_head3_a", [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P])
-_lib.register("pbx_local_head3_b", [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_local_head3_c", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
 # local head: one launch (pbx_local_head_fused) up to LHEAD_FUSED_MAX_B samples per GPU -- 48 / 86 / 165 us
 # against 100 / 197 / 387 us for the five-pass form at B = 512 / 1024 / 2048, L = 512
 # (profiles/r10/lhead_onepass_ubench.txt); larger per-GPU batches, and any the kernel does not support
@@ -58,15 +45,14 @@ def local_head_forward(h: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, y_l:
     st = _s(dev)
     B, L, C = h.shape
     V = wo.shape[0]
-    if batch_softmax.active():
-        return _local_head_dp(h, wo, bo, y_l, w_l, loss_slot)
-    pp = _lib.lib().pbx_local_head_fused_pp(B) if LHEAD_FUSED and B <= LHEAD_FUSED_MAX_B else 0
+    shared = batch_softmax.active()
+    pp = _lib.lib().pbx_local_head_fused_pp(B) if LHEAD_FUSED and B <= LHEAD_FUSED_MAX_B and not shared else 0
+    dh = torch.empty_like(h)
+    dz = torch.empty((B * L, 32), dtype=BF16, device=dev)
     if pp:
         # one launch: a workgroup per position x all samples (the batch reductions stay on chip; no Z /
         # partials workspace, and the loss fold runs over L rows)
         nt = (L + pp - 1) // pp
-        dh = torch.empty_like(h)
-        dz = torch.empty((B * L, 32), dtype=BF16, device=dev)
         dbo_part = torch.empty((nt, V), dtype=F32, device=dev)
         lparts = torch.empty(nt, dtype=F32, device=dev)
         _lib.call("pbx_local_head_fused", h.data_ptr(), wo.detach().contiguous().data_ptr(), bo.data_ptr(),
@@ -74,35 +60,11 @@ def local_head_forward(h: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, y_l:
                   dbo_part.data_ptr(), lparts.data_ptr(), B, L, V, st)
         _lib.call("pbx_colsum_set", lparts.data_ptr(), nt, 1, loss_slot.data_ptr(), None, st)
         return dh, dz, dbo_part
+    # five passes in three stages.  With the batch axis of the softmax shared by the data-parallel group
+    # (``parallel/batch_softmax.py``) stage A leaves the raw (M, S) for the cross-rank merge, and stage B's
+    # T = sum_b G P is summed over ranks before stage C forms dZ = P (G - T).
     nt = _lib.lib().pbx_local_head3_tiles(B, L)          # the kernel's tile grid (16 samples x 32 positions)
     nch = (B + 15) // 16
-    dh = torch.empty_like(h)
-    dz = torch.empty((B * L, 32), dtype=BF16, device=dev)
-    dbo_part = torch.empty((nt, V), dtype=F32, device=dev)
-    lparts = torch.empty(nt, dtype=F32, device=dev)
-    Z = torch.empty((B * L, 32), dtype=F32, device=dev)
-    part = torch.empty((2, nch, L, 32, 2), dtype=F32, device=dev)
-    ms_t = torch.empty((2, L, 32, 2), dtype=F32, device=dev)
-    _lib.call("pbx_local_head3", h.data_ptr(), wo.detach().contiguous().data_ptr(), bo.data_ptr(),
-              y_l.contiguous().data_ptr(), w_l.float().contiguous().data_ptr(), dh.data_ptr(), dz.data_ptr(),
-              dbo_part.data_ptr(), lparts.data_ptr(), Z.data_ptr(), part[0].data_ptr(), part[1].data_ptr(),
-              ms_t[0].data_ptr(), ms_t[1].data_ptr(), B, L, V, st)
-    _lib.call("pbx_colsum_set", lparts.data_ptr(), nt, 1, loss_slot.data_ptr(), None, st)
-    return dh, dz, dbo_part
-
-
-def _local_head_dp(h, wo, bo, y_l, w_l, loss_slot):
-    """The five-pass head with the batch axis of its softmax shared by the data-parallel group
-    (``parallel/batch_softmax.py``): stage A leaves the raw (M, S) for the cross-rank merge, stage B's
-    T = sum_b G P is summed over ranks before stage C forms dZ = P (G - T)."""
-    dev = h.device
-    st = _s(dev)
-    B, L, C = h.shape
-    V = wo.shape[0]
-    nt = _lib.lib().pbx_local_head3_tiles(B, L)
-    nch = (B + 15) // 16
-    dh = torch.empty_like(h)
-    dz = torch.empty((B * L, 32), dtype=BF16, device=dev)
     dbo_part = torch.empty((nt, V), dtype=F32, device=dev)
     lparts = torch.empty(nt, dtype=F32, device=dev)
     Z = torch.empty((B * L, 32), dtype=F32, device=dev)
@@ -112,11 +74,13 @@ def _local_head_dp(h, wo, bo, y_l, w_l, loss_slot):
     y_c = y_l.contiguous()
     w_c = w_l.float().contiguous()
     _lib.call("pbx_local_head3_a", h.data_ptr(), wo_c.data_ptr(), bo.data_ptr(), Z.data_ptr(), part[0].data_ptr(),
-              ms_t[0].data_ptr(), 1, B, L, V, st)
-    batch_softmax.merge_head_stats(ms_t[0])
+              ms_t[0].data_ptr(), int(shared), B, L, V, st)
+    if shared:
+        batch_softmax.merge_head_stats(ms_t[0])
     _lib.call("pbx_local_head3_b", Z.data_ptr(), ms_t[0].data_ptr(), y_c.data_ptr(), w_c.data_ptr(),
               part[1].data_ptr(), lparts.data_ptr(), ms_t[1].data_ptr(), B, L, V, st)
-    batch_softmax.all_reduce_(ms_t[1], "sum")
+    if shared:
+        batch_softmax.all_reduce_(ms_t[1], "sum")
     _lib.call("pbx_local_head3_c", Z.data_ptr(), ms_t[0].data_ptr(), ms_t[1].data_ptr(), y_c.data_ptr(),
               w_c.data_ptr(), wo_c.data_ptr(), bo.data_ptr(), dh.data_ptr(), dz.data_ptr(), dbo_part.data_ptr(),
               B, L, V, st)
@@ -124,17 +88,9 @@ def _local_head_dp(h, wo, bo, y_l, w_l, loss_slot):
     return dh, dz, dbo_part
 
 
-_lib.register("pbx_glob_bwd", [_P, _I, _I, _I, _I, _P, _P])
-_lib.register("pbx_glob3_fwd", [_P, _I, _I, _I, _I, _I, _F, _P])
-_lib.register("pbx_pack_glob_frags", [_P, _P, _P, _I, _I, _P])
-
 LN_EPS = 1e-5
 BF16 = torch.bfloat16
 F32 = torch.float32
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 def _s(dev) -> int:
@@ -253,12 +209,6 @@ def _scratch_like(p: torch.Tensor) -> torch.Tensor:
     return t
 
 
-_lib.register("pbx_ann_supported", [_I, _I, _I])
-_lib.register("pbx_ann_csr", [_P, _I, _I, _P, _P, _P])
-_lib.register("pbx_ann_wt", [_P, _P, _I, _I, _P])
-_lib.register("pbx_ann_fwd", [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_ann_csc", [_P, _I, _I, _P, _P, _P, _P])
-_lib.register("pbx_ann_wgrad", [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
 # sparse GO input layer (csrc/annot.hip) where pbx_ann_supported; the dense MFMA-GEMM form otherwise
 # (tests flip this flag to check both forms)
 ANN_SPARSE = True
@@ -423,10 +373,6 @@ def _ptrs(*ts) -> ctypes.Array:
 def glob_fused_ok(G: int, NGL: int) -> bool:
     """Shapes the fused global-track kernels are compiled for (pbx_glob_supported)."""
     return G in (256, 512) and NGL in (0, 128)
-
-
-_lib.register("pbx_pack_batch", [_P, _P, _I, _P])
-_lib.register("pbx_noop", [_P])
 
 
 def pack_batch(items) -> None:

@@ -19,7 +19,6 @@ Every op raises if the HIP library is missing — there is no silent eager fallb
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import List, Dict, Optional, Tuple
 
@@ -29,35 +28,6 @@ from . import _lib, streams
 from ..train.arena import notify_grads_ready
 from ..utils.determinism import fused_deterministic
 from .global_track import bf16_of
-
-_P, _I, _F, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-
-_lib.register("pbx_conv_fwd3x", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_conv_fwd5x", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_conv_dgrad4x", [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_wgrad2x", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_pack_conv_frag", [_P, _P, _P, _I, _P])
-_lib.register("pbx_wgrad2", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_wgrad_tok", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P])
-_lib.register("pbx_ln_linear_fwd", [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P])
-_lib.register("pbx_pool_fwd", [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P])
-_lib.register("pbx_pool_bwd", [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_ln2_linear_bwd", [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                                     _P, _P, _P, _P, _P, _I, _I, _F, _P, _I, _I, _I, _I, _P])
-_lib.register("pbx_ln2_bwd_slab_rows", [_I, _I, _I])
-_lib.register("pbx_colsum_add", [_P, _I, _I, _P, _P, _P])
-_lib.register("pbx_colsum_add2", [_P, _I, _P, _P, _I, _P, _I, _P])
-_lib.register("pbx_ln1_finalize", [_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _I, _P])
-_lib.register("pbx_embed_fwd", [_P, _P, _P, _L, _P])
-_lib.register("pbx_embed_bwd", [_P, _P, _P, _L, _I, _P, _P])
-_lib.register("pbx_conv_fwd3t", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P])
-_lib.register("pbx_conv_dgrad4f", [_P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
-                                    _F, _P])
-_lib.register("pbx_embed_dpre", [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P])
-_lib.register("pbx_embed_bwd_groups", [_L])
-_lib.register("pbx_conv_fwd_tok_ok", [_I, _I, _I, _I, _I])
-_lib.register("pbx_conv_tok_tables", [_P, _P, _P, _P, _I, _P])
-_lib.register("pbx_conv_fwd_tok", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P])
 
 CH = 128          # kernels are specialised for local_dim = 128
 PB = 32           # positions per workgroup of the position-major LayerNorm kernels
@@ -74,8 +44,7 @@ def conv_tile(L: int) -> int:
     return BM1
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+_p = _lib.ptr
 
 
 # the conv forward: the persistent software-pipelined kernel (csrc/conv5.hip, dilation 5) or conv_fwd3

@@ -20,17 +20,12 @@ The torch oracle is :meth:`...models.proteinbert.GlobalAttention.forward_paper` 
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Optional
 
 import torch
 
 from . import _lib
-
-_P, _I = ctypes.c_void_p, ctypes.c_int
-_lib.register("pbx_paper_attn_fwd", [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P])
-_lib.register("pbx_paper_attn_bwd", [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P])
 
 KEY_DIM = 64
 VALUE_DIM = 128

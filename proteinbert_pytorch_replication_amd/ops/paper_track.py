@@ -17,7 +17,6 @@ kernels.  The global track runs through the fused global-track kernels.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -30,22 +29,6 @@ from .global_track import (BF16, F32, _Grads, _UNIT_LOSS_GRAD, bf16_of, go_head_
 from .local_track import (CH, conv_dgrad, conv_fwd, conv_tile, dwl_slab, pack_conv, _grad_dst, _wgrad,
                           _wgrad_tok, embed_fold_bwd, wgrad_tok_ok)
 
-_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_lib.register("pbx_pc_ln_linear_fwd", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P])
-_lib.register("pbx_pc_ln_linear_bwd", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                       _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_pa_fused_fwd", [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P])
-_lib.register("pbx_paper_head", [_P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_long, _I, _F, _P])
-_lib.register("pbx_paper_head_parts", [ctypes.c_long])
-_lib.register("pbx_pa_fused_bwd", [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P])
-# fp32 query-path GEMMs with fused layouts / epilogues (csrc/sgemm.hip)
-_lib.register("pbx_sg_query_fwd", [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P])
-_lib.register("pbx_sg_query_dg", [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P])
-_lib.register("pbx_sg_query_dwq", [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P])
-_lib.register("pbx_sg_query_ws", [_I, _I, _I, _I])
-_lib.register("pbx_pa_wimg", [_P, _P, _P, _I, _I, _I, _I, _P])
-_lib.register("pbx_group_colsum", [_P, _I, _I, _I, _P, _P])
-
 
 def group_colsum(t: torch.Tensor) -> torch.Tensor:
     """``[G, R, C]`` fp32 -> ``[G, C]``, summed over R in order (``csrc/glob.hip``)."""
@@ -56,7 +39,6 @@ def group_colsum(t: torch.Tensor) -> torch.Tensor:
     out = torch.empty((G, C), dtype=F32, device=t.device)
     _lib.call("pbx_group_colsum", t.data_ptr(), G, R, C, out.data_ptr(), _lib.stream_ptr(t.device))
     return out
-_lib.register("pbx_pa_dwkv_add", [_P, _P, _P, _I, _I, _I, _I, _P])
 
 
 def _sg_ws(B: int, G: int, H: int, K: int, dev) -> torch.Tensor:
