@@ -46,6 +46,14 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// two fp32 -> one dword of two bf16 (a low, b high; RNE, the bits of f2bf) in ONE v_cvt_pk_bf16_f32.  Adjacent
+// scalar conversions pair up only in the SLP vectoriser, which the build turns off: written one by one, a
+// pair costs two converts (one lane used each), a shift and an or.
+__device__ __forceinline__ unsigned f2bf2(float a, float b) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2_t));
+}
+
 // The fused kernels' GELU cores come in two builds of the same sources (ops/build.py):
 //   libpbx_hip.so        the fitted logistic core below (max |err| 2.9e-4 in GELU, 7.8e-4 in GELU', below the
 //                        bf16 rounding of every stored value; 7 / 11 VALU per GELU / GELU + GELU')

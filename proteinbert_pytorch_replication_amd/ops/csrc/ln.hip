@@ -46,6 +46,61 @@ __device__ __forceinline__ uint4 ldq(const bf16_t* p, bool ok) {
   return ok ? *reinterpret_cast<const uint4*>(p) : make_uint4(0u, 0u, 0u, 0u);
 }
 
+// Global accesses of ln2_linear_bwd_kernel's chunk loop are branch-free buffer accesses: a select on a load
+// or an `if` around a store becomes an exec-mask branch, and the wait at its join a vmcnt(0) that retires
+// every store and prefetch in flight.  Loads read a clamped, always-valid address (masked at use); stores of
+// masked lanes get an offset past num_records and are dropped by the range check.
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+constexpr int VO_DROP = 0x7ffffff0;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, bytes, 0x00020000);
+}
+__device__ __forceinline__ uint4 ldq(const __amdgpu_buffer_rsrc_t& rs, int vo) {
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0);
+  return make_uint4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void stq(const __amdgpu_buffer_rsrc_t& rs, int vo, const uint4& q) {
+  __builtin_amdgcn_raw_buffer_store_b128((u32x4){q.x, q.y, q.z, q.w}, rs, vo, 0, 0);
+}
+
+// The compiler's wait for a load is the smallest number of operations issued after it on any path to the use,
+// and a load first used inside a loop stays pending round the loop's back edge.  So before a sample loop
+//  - retire() makes the loop-invariant loads (affine rows, bias) complete, and
+//  - every prefetch issued ahead of the loop is followed by as many dropped stores as one trip of the loop
+//    issues after its own prefetch (dropped_stores; the empty asm statements keep the buffer accesses in the
+//    order written),
+// and the wait at the loop top is then the counted one of the steady state: it leaves the stores of the
+// chunk before outstanding.
+template <int N>
+__device__ __forceinline__ void retire(const float* v) {
+#pragma unroll
+  for (int e = 0; e < N; ++e) asm volatile("" ::"v"(v[e]));
+}
+__device__ __forceinline__ void issue_fence() { asm volatile("" ::: "memory"); }
+// a prefetched tensor's base, its __restrict__ forgotten: loads known not to alias anything move across the
+// fences and the stores
+template <class T>
+__device__ __forceinline__ const T* opaque(const T* p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+template <int N>
+__device__ __forceinline__ void dropped_stores(void* base) {
+  const __amdgpu_buffer_rsrc_t none = buf_rsrc(base, 0);
+  issue_fence();
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    __builtin_amdgcn_raw_buffer_store_b32(0u, none, VO_DROP - 16 * i, 0, 0);
+    issue_fence();
+  }
+}
+
+// samples of s1 a thread of ln_linear_fwd_kernel prefetches ahead of the one it computes.  A deeper ring
+// (2 - 8, branch-free buffer accesses and counted waits as in ln2_linear_bwd_kernel) measured 3 - 11 %
+// slower at B = 2048, L = 512 (profiles/r12/ln_kernels_ubench.txt): the kernel does not wait for HBM.
+constexpr int FWD_RING = 1;
+
 // per-sample statistics through LDS (computed by one wave, broadcast)
 __device__ __forceinline__ void sample_stats(float* sh, const float* __restrict__ st, int T, int BM, int L, float eps,
                                              const float* __restrict__ sums, int Ts, float inv_n) {
@@ -230,6 +285,8 @@ __global__ void __launch_bounds__(512) ln2_linear_bwd_kernel(
   const int nsplit = gridDim.y;
   const int b0 = (int)((long)B * blockIdx.y / nsplit), b1 = (int)((long)B * (blockIdx.y + 1) / nsplit);
   stage_weight(ws, wl, CH);
+  const bf16_t *const dh2o = opaque(dh2), *const s2o = opaque(s2), *const pre_lo = opaque(pre_l), *const s1o = opaque(s1);
+  const float* const constso = opaque(consts);
   float adbl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // dWl accumulators: wave w owns co tile (w >> 1) and ci tiles 2 (w & 1) + {0, 1}; they sum over every
   // pair the workgroup walks (long sequences: fewer workgroups than pairs, so fewer dWl flushes)
@@ -238,35 +295,63 @@ __global__ void __launch_bounds__(512) ln2_linear_bwd_kernel(
   for (int pair = blockIdx.x; pair < TS1; pair += gridDim.x) {
     const int l = pair * 2 + (j & 1);
     const bool okl = l < L;
-    float ga2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ga1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bt1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (okl) {
-      load_f8(g2 + (size_t)l * CH + ch * 8, ga2);
-      load_f8(g1 + (size_t)l * CH + ch * 8, ga1);
-      load_f8(be1 + (size_t)l * CH + ch * 8, bt1);
+    // loads read row min(l, L - 1) of sample min(bs, b1 - 1) and are masked at use (the zero rows and unit
+    // constants a skipped load stood for)
+    const int coff = min(l, L - 1) * CH + ch * 8;
+    float ga2[8], ga1[8], bt1[8];
+    load_f8(g2 + coff, ga2);
+    load_f8(g1 + coff, ga1);
+    load_f8(be1 + coff, bt1);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      ga2[e] = okl ? ga2[e] : 0.f;
+      ga1[e] = okl ? ga1[e] : 0.f;
+      bt1[e] = okl ? bt1[e] : 0.f;
     }
+    retire<8>(ga2);
+    retire<8>(ga1);
+    retire<8>(bt1);
     float adg2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, adb2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float adg1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, adb1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const size_t coff = (size_t)l * CH + ch * 8;
-    // prefetch the first chunk
-    int bs = b0 + (j >> 1);
-    bool ok = okl && bs < b1;
-    size_t off = (size_t)bs * L * CH + coff;
-    uint4 n_dh = ldq(dh2 + off, ok), n_s2 = ldq(s2 + off, ok), n_s1 = ldq(s1 + off, ok);
-    uint4 n_pr = ldq(pre_l + off, ok);
-    float4 n_c0 = make_float4(0.f, 1.f, 0.f, 0.f), n_c1 = make_float4(0.f, 1.f, 0.f, 0.f);
-    if (bs < b1) {
-      n_c0 = *reinterpret_cast<const float4*>(consts + (size_t)bs * 8);
-      n_c1 = *reinterpret_cast<const float4*>(consts + (size_t)bs * 8 + 4);
-    }
+    const int blast = max(b1 - 1, 0);
+    // a chunk's accesses go through resources over its (up to 16) samples, so stores of samples past b1
+    // fall outside them; rows past L and the lanes that hold no sums1 pair get VO_DROP
+    const int vo_dh = okl ? (((j >> 1) * L + l) * CH + ch * 8) * 2 : VO_DROP;
+    const int vo_su = (lane & 31) == 0 ? ((j >> 1) * TS1 + pair) * 8 : VO_DROP;
+    bool ok, okb;
+    uint4 n_dh, n_s2, n_pr, n_s1;
+    float4 n_c0, n_c1;
+    auto prefetch = [&](int bc) {
+      const int bs = bc + (j >> 1);
+      okb = bs < b1;
+      ok = okl && okb;
+      const int cb = min(bc, blast), ns = min(b1 - cb, 16);            // (the chunk past the end: sample b1 - 1)
+      const int sm = min(bs, blast) - cb;
+      const int vl = (sm * L * CH + coff) * 2, bytes = ns * L * CH * 2;
+      const size_t base = (size_t)cb * L * CH;
+      n_dh = ldq(buf_rsrc(dh2o + base, bytes), vl);
+      n_s2 = ldq(buf_rsrc(s2o + base, bytes), vl);
+      n_pr = ldq(buf_rsrc(pre_lo + base, bytes), vl);
+      n_s1 = ldq(buf_rsrc(s1o + base, bytes), vl);
+      const __amdgpu_buffer_rsrc_t rc = buf_rsrc(constso + (size_t)cb * 8, ns * 32);
+      const uint4 q0 = ldq(rc, sm * 32), q1 = ldq(rc, sm * 32 + 16);
+      n_c0 = make_float4(__uint_as_float(q0.x), __uint_as_float(q0.y), __uint_as_float(q0.z), __uint_as_float(q0.w));
+      n_c1 = make_float4(__uint_as_float(q1.x), __uint_as_float(q1.y), __uint_as_float(q1.z), __uint_as_float(q1.w));
+    };
+    // the first chunk; a trip of the loop is (prefetch, dh1 store, sums1 store)
+    issue_fence();
+    prefetch(b0);
+    dropped_stores<2>(dh1);
     for (int bc = b0; bc < b1; bc += 16) {
-      const int bcur = bs;
       const bool okc = ok;
-      const size_t offc = off;
-      const float mean2 = n_c0.x, rstd2 = n_c0.y, m1 = n_c0.z, m2 = n_c0.w, mean1 = n_c1.x, rstd1 = n_c1.y;
+      const uint4 zq = make_uint4(0u, 0u, 0u, 0u);
+      const float4 c0 = okb ? n_c0 : make_float4(0.f, 1.f, 0.f, 0.f);
+      const float4 c1 = okb ? n_c1 : make_float4(0.f, 1.f, 0.f, 0.f);
+      const float mean2 = c0.x, rstd2 = c0.y, m1 = c0.z, m2 = c0.w, mean1 = c1.x, rstd1 = c1.y;
       float dh[8], sv2[8], pr[8], sv1[8], ds2[8], dp[8], xh1[8], hv[8];
-      unpack8(n_dh, dh);
-      unpack8(n_s2, sv2);
-      unpack8(n_s1, sv1);
+      unpack8(okc ? n_dh : zq, dh);
+      unpack8(okc ? n_s2 : zq, sv2);
+      unpack8(okc ? n_s1 : zq, sv1);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float xh2 = (sv2[e] - mean2) * rstd2;
@@ -277,20 +362,7 @@ __global__ void __launch_bounds__(512) ln2_linear_bwd_kernel(
         hv[e] = okc ? xh1[e] * ga1[e] + bt1[e] : 0.f;
       }
       *reinterpret_cast<uint4*>(ht + swz256(j, ch)) = packq8(hv);
-      auto prefetch = [&]() {
-        bs = bc + 16 + (j >> 1);
-        ok = okl && bs < b1;
-        off = (size_t)bs * L * CH + coff;
-        n_dh = ldq(dh2 + off, ok);
-        n_s2 = ldq(s2 + off, ok);
-        n_pr = ldq(pre_l + off, ok);
-        n_s1 = ldq(s1 + off, ok);
-        if (bs < b1) {
-          n_c0 = *reinterpret_cast<const float4*>(consts + (size_t)bs * 8);
-          n_c1 = *reinterpret_cast<const float4*>(consts + (size_t)bs * 8 + 4);
-        }
-      };
-      unpack8(n_pr, pr);
+      unpack8(okc ? n_pr : zq, pr);
       float gp[8];
       {
         const f32x2 xi[4] = {(f32x2){pr[0], pr[1]}, (f32x2){pr[2], pr[3]}, (f32x2){pr[4], pr[5]},
@@ -314,8 +386,9 @@ __global__ void __launch_bounds__(512) ln2_linear_bwd_kernel(
         for (int e = 0; e < 8; ++e) adbl[e] += dpr[e];
       }
       __syncthreads();
-      // prefetch the next chunk while the MFMAs run
-      prefetch();
+      // prefetch the next chunk while the MFMAs run (issued before this chunk's stores, so the wait for
+      // it at the loop top leaves them outstanding)
+      prefetch(bc + 16);
       if (w < 4) {
         // D[ci][row] = sum_co Wl[co][ci] dpre[row][co]: A = Wl^T (transposed LDS read), B = dpre rows
         f32x16_t acc = zero16();
@@ -347,26 +420,29 @@ __global__ void __launch_bounds__(512) ln2_linear_bwd_kernel(
       const float4 yb = *reinterpret_cast<const float4*>(yt + j * YS + ch * 8 + 4);
       const float yv[8] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w};
       float o[8], sa = 0.f, sc = 0.f;
+      // o = the bf16-rounded dh1 (0 where masked): packed once, the sums take the stored values
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = okc ? ds2[e] + yv[e] : 0.f;
+      const uint4 oq = packq8(o);
+      unpack8(oq, o);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        o[e] = okc ? bfround(ds2[e] + yv[e]) : 0.f;
         const float dxh = o[e] * ga1[e];
         sa += dxh;
         sc += dxh * xh1[e];
         adg1[e] += o[e] * xh1[e];
         adb1[e] += o[e];
       }
-      if (okc) *reinterpret_cast<uint4*>(dh1 + offc) = packq8(o);
+      const int nsmp = min(b1 - bc, 16);
+      stq(buf_rsrc(dh1 + (size_t)bc * L * CH, nsmp * L * CH * 2), vo_dh, oq);
       // LN1 partial of (sample, position pair): 16 lanes per row, rows j and j+1 share the sample
 #pragma unroll
       for (int m = 1; m <= 16; m <<= 1) {
         sa += __shfl_xor(sa, m, 64);
         sc += __shfl_xor(sc, m, 64);
       }
-      if ((lane & 31) == 0 && bcur < b1) {
-        sums1[((size_t)bcur * TS1 + pair) * 2] = sa;
-        sums1[((size_t)bcur * TS1 + pair) * 2 + 1] = sc;
-      }
+      __builtin_amdgcn_raw_buffer_store_b64((u32x2){__float_as_uint(sa), __float_as_uint(sc)},
+                                            buf_rsrc(sums1 + (size_t)bc * TS1 * 2, nsmp * TS1 * 8), vo_su, 0, 0);
     }
     // [L, C] affine gradients: sum the 16 rows of each position through LDS, one add per element
     const int l0 = pair * 2;
@@ -640,6 +716,9 @@ static int ln_groups(int B, int L) {
   int g = (2 * num_cus() + tp - 1) / tp;          // ~2 workgroups of 8 waves per CU
   return g < 1 ? 1 : (g > B ? B : g);
 }
+
+// samples a thread of ln_linear_fwd_kernel prefetches ahead (tests size their batches around it)
+PBX_EXPORT int pbx_ln_fwd_ring(void) { return FWD_RING; }
 
 // pre_l (nullable): the MLP pre-activation for the backward (inference forwards skip it)
 PBX_EXPORT int pbx_ln_linear_fwd(const void* s1, const float* st1, int T1, int BM1, const float* g1,

@@ -71,10 +71,10 @@ __device__ __forceinline__ int tr_c(int lane) { return ((lane & 3) << 2) + (((la
 
 // 8 fp32 -> bf16x8 (RNE)
 __device__ __forceinline__ bf16x8 pack8(const float* v) {
-  typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
-  u16x8 u;
+  typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+  u32x4_t u;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) u[i] = f2bf(v[i]);
+  for (int i = 0; i < 4; ++i) u[i] = f2bf2(v[2 * i], v[2 * i + 1]);
   return __builtin_bit_cast(bf16x8, u);
 }
 
@@ -90,16 +90,16 @@ __device__ __forceinline__ void unpack4(const uint2& q, float* v) {
 }
 __device__ __forceinline__ uint4 packq8(const float* v) {
   uint4 q;
-  q.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
-  q.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
-  q.z = (unsigned)f2bf(v[4]) | ((unsigned)f2bf(v[5]) << 16);
-  q.w = (unsigned)f2bf(v[6]) | ((unsigned)f2bf(v[7]) << 16);
+  q.x = f2bf2(v[0], v[1]);
+  q.y = f2bf2(v[2], v[3]);
+  q.z = f2bf2(v[4], v[5]);
+  q.w = f2bf2(v[6], v[7]);
   return q;
 }
 __device__ __forceinline__ uint2 packq4(const float* v) {
   uint2 q;
-  q.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
-  q.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
+  q.x = f2bf2(v[0], v[1]);
+  q.y = f2bf2(v[2], v[3]);
   return q;
 }
 __device__ __forceinline__ float bfround(float f) { return bf2f(f2bf(f)); }
