@@ -10,7 +10,8 @@ __version__ = "0.1.0"
 from .config import (ModelConfig, DataConfig, OptimConfig, DistConfig, KernelConfig, TrainConfig,
                      RunConfig, PRESETS, get_preset, apply_overrides, load_yaml)
 from .models import ProteinBERT, ProteinBERTBlock, GlobalAttention, build_model
+from .inference import Predictor
 
 __all__ = ["ModelConfig", "DataConfig", "OptimConfig", "DistConfig", "KernelConfig", "TrainConfig",
            "RunConfig", "PRESETS", "get_preset", "apply_overrides", "load_yaml", "ProteinBERT",
-           "ProteinBERTBlock", "GlobalAttention", "build_model", "__version__"]
+           "ProteinBERTBlock", "GlobalAttention", "build_model", "Predictor", "__version__"]

@@ -6,6 +6,7 @@ COMMANDS = {
     "create-uniref-h5-db": ("etl", "main_uniref_h5"),
     "pretrain": ("train", "pretrain_main"),
     "finetune": ("train", "finetune_main"),
+    "predict": ("predict", "main"),
     "dummy-tests": ("dummy_tests", "main"),
 }
 

@@ -1,0 +1,237 @@
+"""Using a pretrained ProteinBERT as a model: embeddings, GO-term predictions and residue calls.
+
+:class:`Predictor` wraps a :class:`~.models.ProteinBERT` and answers, for a list of protein sequences (or
+token tensors), any subset of
+
+===================  ==========================================================  =======================
+``outputs`` name     entries of the result                                       dtype
+===================  ==========================================================  =======================
+``global``           ``global`` ``[N, G]``: the global track's final vector      fp32
+``pooled``           ``pooled`` ``[N, 128]``: mean of the local track over the   fp32
+                     non-``<pad>`` positions
+``residue``          ``residue`` ``[N, L, 128]``: the local track                bf16 (HIP) / fp32
+``go_probs``         ``go_probs`` ``[N, A]``                                     fp32
+``go_topk``          ``go_topk_values`` / ``go_topk_indices`` ``[N, k]``         fp32 / int32
+``residue_probs``    ``residue_probs`` ``[N, L, V]``                             fp32
+``residue_tokens``   ``residue_tokens`` / ``residue_token_probs`` ``[N, L]``     int32 / fp32
+``hidden_states``    ``hidden_global`` ``[N, blocks, G]`` / ``hidden_pooled``    fp32
+                     ``[N, blocks, 128]``: ``global`` / ``pooled`` after every
+                     block
+===================  ==========================================================  =======================
+
+Only the requested heads run.  On the HIP backend (``model.resolved_backend(device) == "hip"``) the encoder is
+:func:`.ops.fused_model.fused_encode` and the heads are the fused kernels of :mod:`.ops.infer_heads`; on the
+PyTorch backend the same outputs come from ``encode_torch`` + ``heads_torch`` with the same tie rules (GO
+top-k: descending, equal probabilities by ascending index, a stable sort; residue call: the first maximal
+index; pooling: a masked mean in fp32).
+
+**Reference semantics: local predictions depend on batch mates.**  The reference's local head normalises
+every (position, token) over the BATCH axis (``modules.py:277-284``), so ``residue_probs`` /
+``residue_tokens`` / ``residue_token_probs`` of a sequence change with the sequences it shares a batch with,
+and a batch of one gives probabilities of exactly 1 everywhere.  That is the reference's behaviour and is not
+corrected here: :meth:`Predictor.predict` normalises over each of its batches of ``batch_size`` sequences (the
+last one may be smaller), on this process only.  Keep ``batch_size`` and the input order fixed to compare
+runs, or use a ``semantics="paper"`` model (softmax over the vocabulary), whose predictions are per sequence.
+Embeddings and GO predictions do not depend on the batch in either semantics.
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, List, Optional, Sequence, Union
+
+import torch
+
+from .data.transforms import SimpleCharacterTokenizer, pad_to
+from .data.vocab import PAD_ID, create_amino_acid_vocab
+
+OUTPUTS = ("global", "pooled", "residue", "go_probs", "go_topk", "residue_probs", "residue_tokens", "hidden_states")
+DEFAULT_OUTPUTS = ("global", "pooled", "go_topk")
+
+
+def _check_outputs(outputs: Iterable[str]) -> tuple:
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    outputs = tuple(outputs)
+    bad = [o for o in outputs if o not in OUTPUTS]
+    if bad:
+        raise ValueError(f"unknown outputs {bad}: expected a subset of {OUTPUTS}")
+    return outputs
+
+
+def masked_mean_torch(h: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """fp32 mean of ``h [B, L, C]`` over the positions with ``tokens != <pad>``; zeros where there is none."""
+    m = (tokens != PAD_ID).unsqueeze(-1)
+    s = (h.float() * m).sum(dim=1)
+    n = m.sum(dim=1)
+    return torch.where(n > 0, s / n.clamp(min=1), torch.zeros_like(s))
+
+
+def stable_topk_torch(p: torch.Tensor, k: int):
+    """``(values [B, k], indices [B, k] int32)``: descending, equal values by ascending index."""
+    v, i = torch.sort(p, dim=-1, descending=True, stable=True)
+    return v[:, :k].contiguous(), i[:, :k].to(torch.int32).contiguous()
+
+
+class Predictor:
+    """Inference on ``model`` (see the module docstring for the outputs and for how reference-semantics local
+    predictions depend on the batch).  ``batch_size``: sequences per encoder pass of :meth:`predict`;
+    ``device``: where the model runs (default: where its parameters are)."""
+
+    def __init__(self, model, batch_size: int = 256, device=None):
+        if batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        self.model = model
+        self.batch_size = int(batch_size)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        self.tokenizer = SimpleCharacterTokenizer(create_amino_acid_vocab(), add_sos_eos=True)
+
+    # ------------------------------------------------------------------------
+    def tokenize(self, sequences: Sequence[str], truncate: bool = False) -> torch.Tensor:
+        """``<sos>`` residues ``<eos>``, padded to ``model.sequences_length``: int64 ``[N, L]`` on the CPU.  A
+        sequence of more than ``L - 2`` residues raises ``ValueError`` unless ``truncate`` keeps its first
+        ``L - 2``."""
+        L = self.model.sequences_length
+        rows = []
+        for n, s in enumerate(sequences):
+            if not isinstance(s, str):
+                raise TypeError(f"sequence {n}: expected a string, got {type(s).__name__}")
+            if len(s) > L - 2:
+                if not truncate:
+                    raise ValueError(f"sequence {n} has {len(s)} residues, the model takes at most {L - 2} "
+                                     f"(pass truncate=True to keep the first {L - 2})")
+                s = s[:L - 2]
+            rows.append(pad_to(self.tokenizer.encode_np(s), L))
+        return torch.stack(rows) if rows else torch.zeros((0, L), dtype=torch.long)
+
+    def _annotations(self, annotations, n: int, device) -> torch.Tensor:
+        A = self.model.config["num_annotations"]
+        if annotations is None:                     # "no GO prior", as models/finetune._split_inputs
+            return torch.zeros((n, A), dtype=torch.float32, device=device)
+        return annotations.to(device, non_blocking=True).float()
+
+    # ------------------------------------------------------------------------
+    def predict_batch(self, tokens: torch.Tensor, annotations: Optional[torch.Tensor] = None,
+                      outputs: Iterable[str] = DEFAULT_OUTPUTS, go_top_k: int = 10) -> Dict[str, torch.Tensor]:
+        """One encoder pass over ``tokens [B, L]`` int64 (and ``annotations [B, A]``, zeros when None):
+        the requested outputs as tensors on the model's device, without any host synchronisation."""
+        outputs = _check_outputs(outputs)
+        model = self.model
+        A = model.config["num_annotations"]
+        if ("go_topk" in outputs) and not 1 <= go_top_k <= A:
+            raise ValueError(f"go_top_k={go_top_k}: expected 1 .. {A}")
+        tokens = tokens.to(self.device, non_blocking=True)
+        ann = self._annotations(annotations, tokens.shape[0], self.device)
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                if model.resolved_backend(self.device) == "hip":
+                    return self._predict_hip(tokens, ann, outputs, go_top_k)
+                return self._predict_torch(tokens, ann, outputs, go_top_k)
+        finally:
+            model.train(was_training)
+
+    def _predict_hip(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
+        from .ops import infer_heads as ih
+        from .ops.fused_model import fused_encode
+        model = self.model
+        tokens = tokens.contiguous()
+        hidden_g: List[torch.Tensor] = []
+        hidden_p: List[torch.Tensor] = []
+
+        def tap(i, h_i, g_i):
+            hidden_g.append(g_i)
+            hidden_p.append(ih.masked_mean_pool(h_i.contiguous(), tokens))      # one pool launch per block
+
+        want_hidden = "hidden_states" in outputs
+        h, g, g_bf = fused_encode(model, tokens, ann, return_bf16=True, tap=tap if want_hidden else None)
+        h = h.contiguous()
+        out: Dict[str, torch.Tensor] = {}
+        if "global" in outputs:
+            out["global"] = g
+        if "pooled" in outputs:
+            out["pooled"] = hidden_p[-1] if want_hidden else ih.masked_mean_pool(h, tokens)
+        if "residue" in outputs:
+            out["residue"] = h
+        if "go_probs" in outputs or "go_topk" in outputs:
+            go = model.pretraining_global_output[0]
+            p = ih.go_probs(g_bf, go.weight, go.bias)
+            if "go_probs" in outputs:
+                out["go_probs"] = p
+            if "go_topk" in outputs:
+                v, i = ih.row_topk(p, k) if ih.topk_supported(p.shape[1], k) else stable_topk_torch(p, k)
+                out["go_topk_values"], out["go_topk_indices"] = v, i
+        if "residue_probs" in outputs or "residue_tokens" in outputs:
+            P, tok, pmax = ih.local_probs(model, h, store_probs="residue_probs" in outputs)
+            if "residue_probs" in outputs:
+                out["residue_probs"] = P
+            if "residue_tokens" in outputs:
+                out["residue_tokens"], out["residue_token_probs"] = tok, pmax
+        if want_hidden:
+            out["hidden_global"] = torch.stack(hidden_g, dim=1)
+            out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
+        return out
+
+    def _predict_torch(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
+        model = self.model
+        hidden_g: List[torch.Tensor] = []
+        hidden_p: List[torch.Tensor] = []
+
+        def tap(i, h_i, g_i):
+            hidden_g.append(g_i.float())
+            hidden_p.append(masked_mean_torch(h_i, tokens))
+
+        want_hidden = "hidden_states" in outputs
+        h, g = model.encode_torch(tokens, ann, tap=tap if want_hidden else None)
+        out: Dict[str, torch.Tensor] = {}
+        if "global" in outputs:
+            out["global"] = g.float()
+        if "pooled" in outputs:
+            out["pooled"] = masked_mean_torch(h, tokens)
+        if "residue" in outputs:
+            out["residue"] = h
+        heads = {"go_probs", "go_topk", "residue_probs", "residue_tokens"} & set(outputs)
+        if heads:
+            pl, pg = model.heads_torch(h, g)
+            if "go_probs" in outputs:
+                out["go_probs"] = pg
+            if "go_topk" in outputs:
+                out["go_topk_values"], out["go_topk_indices"] = stable_topk_torch(pg, k)
+            if "residue_probs" in outputs:
+                out["residue_probs"] = pl
+            if "residue_tokens" in outputs:
+                tok = pl.argmax(dim=-1)                                 # the first maximal index on ties
+                out["residue_tokens"] = tok.to(torch.int32)
+                out["residue_token_probs"] = pl.gather(-1, tok.unsqueeze(-1)).squeeze(-1)
+        if want_hidden:
+            out["hidden_global"] = torch.stack(hidden_g, dim=1)
+            out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
+        return out
+
+    # ------------------------------------------------------------------------
+    def predict(self, sequences: Union[Sequence[str], torch.Tensor], annotations: Optional[torch.Tensor] = None,
+                outputs: Iterable[str] = DEFAULT_OUTPUTS, go_top_k: int = 10,
+                truncate: bool = False) -> Dict[str, torch.Tensor]:
+        """Predictions for ``sequences`` (a list of strings, tokenised by :meth:`tokenize`; or an int64 token
+        tensor ``[N, L]``, taken as it is) in batches of ``batch_size``: CPU tensors in input order.  No host
+        synchronisation per batch: every batch's outputs are copied, without blocking, into host tensors
+        allocated once (pinned when the model is on a GPU), and the device is synchronised once at the end."""
+        outputs = _check_outputs(outputs)
+        tokens = sequences if isinstance(sequences, torch.Tensor) else self.tokenize(list(sequences), truncate)
+        if tokens.dim() != 2 or tokens.dtype != torch.int64:
+            raise ValueError("token input must be an int64 [N, L] tensor")
+        N = tokens.shape[0]
+        if annotations is not None and annotations.shape[0] != N:
+            raise ValueError(f"{annotations.shape[0]} annotation rows for {N} sequences")
+        cuda = self.device.type == "cuda"
+        host: Dict[str, torch.Tensor] = {}
+        for s in range(0, N, self.batch_size):
+            e = min(N, s + self.batch_size)
+            out = self.predict_batch(tokens[s:e], None if annotations is None else annotations[s:e], outputs,
+                                     go_top_k)
+            for name, t in out.items():
+                if name not in host:
+                    host[name] = torch.empty((N,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=cuda)
+                host[name][s:e].copy_(t, non_blocking=True)
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        return host

@@ -357,15 +357,18 @@ class ProteinBERT(nn.Module):
 
     def encode_torch(self, tokens: torch.Tensor, annotations: torch.Tensor,
                      compute_dtype: Optional[torch.dtype] = None,
-                     faithful_attention: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                     faithful_attention: bool = False, tap=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``tap``: called as ``tap(i, h_i, g_i)`` after block ``i`` with that block's outputs."""
         self.check_length(tokens.shape[1])
         dt = compute_dtype or torch.float32
         h = self.local_embedding.weight.to(dt)[tokens]                       # [B,L,C]
         lin = self.global_linear_layer[0]
         g = _gelu(F.linear(annotations.to(dt), lin.weight.to(dt), lin.bias.to(dt))).float()
         mask = tokens != 0 if self.semantics == "paper" else None
-        for blk in self.proteinBERT_blocks:
+        for i, blk in enumerate(self.proteinBERT_blocks):
             h, g = blk.forward_torch(h, g, mask, faithful_attention)
+            if tap is not None:
+                tap(i, h, g)
         return h, g
 
     def heads_torch(self, h: torch.Tensor, g: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -27,6 +27,11 @@
 // entry with weight > 0 is counted into one of two per-workgroup LDS histograms of 256 bins of p (y = 1 /
 // y = 0, bin = min(255, (int)(p * 256))) with LDS integer atomics, and each workgroup stores its 2 x 256
 // bins to its own row of a partial buffer (no global atomics: results are bitwise repeatable).
+//
+// EPI_GO_PROB: the head for inference (ops/infer_heads.py): the same main loop and tile transpose, the
+// training head's p = 1 / (1 + exp(-(acc + bias))) per element, stored as fp32 rows of P [M][ldp] (two
+// 16-B stores per 8-column chunk where aligned; columns >= N are not written).  No targets, no weights,
+// no loss; z is never stored.
 #include "mfma.h"
 
 using namespace pbx;
@@ -37,7 +42,7 @@ constexpr int BT = 128;   // tile rows / cols
 constexpr int BK = 128;   // K chunk
 constexpr int TILE = BT * 256;   // bytes of one staged operand tile
 
-enum { EPI_STORE = 0, EPI_GO = 1, EPI_GO_EVAL = 2 };
+enum { EPI_STORE = 0, EPI_GO = 1, EPI_GO_EVAL = 2, EPI_GO_PROB = 3 };
 constexpr int GO_BINS = 256;   // EPI_GO_EVAL: histogram bins of p per class
 
 struct GoArgs {
@@ -210,6 +215,45 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const bf16_t* __restrict__
   gemm_mainloop<TA, TB, AL_A, AL_B>(acc, smem, A, lda, B, ldb, M, N, K, m0, n0, kc0, kc1);
   if constexpr (EPI == EPI_STORE) {
     gemm_store(acc, C + (size_t)blockIdx.z * M * ldc, ldc, M, N, m0, n0, accumulate);   // split-K slab z
+  } else if constexpr (EPI == EPI_GO_PROB) {
+    // probabilities only: the tile through LDS as below, then per thread a fixed 8-column group over 8 rows
+    constexpr int TS = BT + 4;
+    float* ft = reinterpret_cast<float*>(smem);
+    __syncthreads();                                  // staging tiles no longer read
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          ft[(wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) * TS + wn * 64 + j * 32 + r] = acc[i][j][e];
+    __syncthreads();
+    const int c8 = tid & 15, rg = tid >> 4;           // columns n0 + 8 c8 .. +7, rows rg + 16 k
+    const int nb = n0 + 8 * c8;
+    float bc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bc[e] = nb + e < N ? go.bias[nb + e] : 0.f;
+    const bool vec = nb + 8 <= N && (ldc % 4) == 0 && ((uintptr_t)C & 15) == 0;
+#pragma unroll 2
+    for (int k = 0; k < 8; ++k) {
+      const int rl = rg + 16 * k, m = m0 + rl;
+      if (m >= M) break;
+      const float4 z0 = *reinterpret_cast<const float4*>(ft + rl * TS + 8 * c8);
+      const float4 z1 = *reinterpret_cast<const float4*>(ft + rl * TS + 8 * c8 + 4);
+      const float zz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
+      float p[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) p[e] = 1.0f / (1.0f + __expf(-(zz[e] + bc[e])));
+      float* prow = C + (size_t)m * ldc + nb;
+      if (vec) {
+        *reinterpret_cast<float4*>(prow) = make_float4(p[0], p[1], p[2], p[3]);
+        *reinterpret_cast<float4*>(prow + 4) = make_float4(p[4], p[5], p[6], p[7]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (nb + e < N) prow[e] = p[e];
+      }
+    }
   } else {
     // GO head.  The 128 x 128 fp32 tile goes through LDS (row stride 132 floats) so the epilogue
     // runs on row-contiguous 8-column chunks: 2 x 16-B loads of y, one 16-B dz store, per thread a fixed
@@ -414,7 +458,7 @@ template <int TA, int TB, bool AL_A, bool AL_B, int EPI>
 int launch(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, int K, int splitk,
            int accumulate, const GoArgs& go, hipStream_t st) {
   // GO: the fp32 tile for the epilogue; GO_EVAL: + the two histograms (69632 B: two workgroups per CU)
-  constexpr int lds = EPI == EPI_GO ? BT * (BT + 4) * 4
+  constexpr int lds = EPI == EPI_GO || EPI == EPI_GO_PROB ? BT * (BT + 4) * 4
                       : EPI == EPI_GO_EVAL ? BT * (BT + 4) * 4 + 2 * GO_BINS * 4 : 2 * TILE;
   static bool attr = false;
   if (!attr) {
@@ -495,6 +539,17 @@ PBX_EXPORT int pbx_go_head_eval(const void* x, long ldx, const void* w, long ldw
   GoArgs go{bias, y, ldy, wrow, wfull, nullptr, 0, nullptr, loss_part, 1.0f / ((float)M * (float)N), hist_part};
   const bool aa = aligned(x, ldx, K, false), ab = aligned(w, ldw, K, false);
   return dispatch_al<0, 1, EPI_GO_EVAL>(aa, ab, x, ldx, w, ldw, nullptr, 0, M, N, K, 1, 0, go, st);
+}
+
+// The GO head's probabilities for inference (EPI_GO_PROB): x [M = B][K = G] bf16, w [N = A][K] bf16 and bias
+// [A] as pbx_go_head_fused; output P [B][ldp] fp32, p = sigmoid(x w^T + bias), columns A .. ldp untouched.
+PBX_EXPORT int pbx_go_head_probs(const void* x, long ldx, const void* w, long ldw, const float* bias, float* P,
+                                 long ldp, int M, int N, int K, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || ldp < N || P == nullptr || bias == nullptr) return (int)hipErrorInvalidValue;
+  GoArgs go{};
+  go.bias = bias;
+  const bool aa = aligned(x, ldx, K, false), ab = aligned(w, ldw, K, false);
+  return dispatch_al<0, 1, EPI_GO_PROB>(aa, ab, x, ldx, w, ldw, P, ldp, M, N, K, 1, 0, go, st);
 }
 
 // n (<= 4) GEMMs C_i (+)= op(A_i) op(B_i) of one (ta, tb) class in one launch (no split-K).

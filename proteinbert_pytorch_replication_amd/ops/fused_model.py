@@ -48,8 +48,11 @@ def _check(model) -> None:
 
 
 def fused_encode(model, tokens: torch.Tensor, annotations: torch.Tensor,
-                 return_bf16: bool = False, cp=None):
+                 return_bf16: bool = False, cp=None, tap=None):
     """Encoder on the HIP path: returns ``h [B, L, 128]`` (bf16) and ``g [B, G]`` (fp32).
+
+    ``tap``: called as ``tap(i, h_i, g_i)`` after block ``i`` with that block's outputs (the per-block
+    representations of :mod:`..inference`); ``None`` changes nothing.
 
     ``cp`` (:class:`..parallel.cp_fused.CPShard`): ``tokens`` is this rank's slice of the sequence;
     the local track runs on the slice (halo rows and LayerNorm statistics exchanged inside the block),
@@ -137,6 +140,8 @@ def fused_encode(model, tokens: torch.Tensor, annotations: torch.Tensor,
             g, g_bf, gb = FusedGlobalBlockFn.apply(*args, glob_imgs[i])
         else:
             g, g_bf, gb = GlobalBlockFn.apply(*args)
+        if tap is not None:
+            tap(i, h, g)
     if return_bf16:
         return h, g, g_bf
     return h, g

@@ -1,0 +1,149 @@
+"""Prediction heads for inference (``csrc/infer.hip``, ``EPI_GO_PROB`` in ``csrc/gemm.hip``).
+
+The training heads produce a loss and gradients, the evaluation heads (:mod:`.eval_heads`) loss partials and
+counts; neither returns a prediction.  Here each head writes what :mod:`..inference` hands to the caller:
+
+* :func:`go_probs` -- the GO head as one MFMA GEMM launch whose epilogue stores ``sigmoid(z)`` (``z`` is never
+  stored, no elementwise pass follows);
+* :func:`row_topk` -- the ``k`` largest entries of every row, descending, equal values in ascending index
+  order (``torch.sort(descending=True, stable=True)[:k]``), one wave per row with the row in registers;
+* :func:`local_probs` -- the local head of either semantics: optional probabilities ``[B, L, V]``, the called
+  token of every position (the lowest index of the maximum of the stored probabilities) and its probability;
+* :func:`masked_mean_pool` -- the mean of ``h`` over the non-``<pad>`` positions.
+
+No autograd Function is involved, nothing is kept for a backward pass, and every output is bitwise repeatable.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from .global_track import bf16_of
+
+F32 = torch.float32
+TOPK_MAX_K = 64                 # pbx_row_topk: results live one per lane of a wave
+TOPK_MAX_COLS = 256 * 64        # ... and the row in registers, at most 256 values per lane
+
+
+def _s(dev) -> int:
+    return _lib.stream_ptr(dev)
+
+
+def topk_supported(A: int, k: int) -> bool:
+    """Whether :func:`row_topk` takes ``k`` of ``A`` columns (outside: ``torch.sort(..., stable=True)``)."""
+    return 1 <= A <= TOPK_MAX_COLS and 1 <= k <= min(TOPK_MAX_K, A)
+
+
+def go_probs(g_bf: torch.Tensor, wa: torch.Tensor, ba: torch.Tensor,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``sigmoid(g_bf Wa^T + ba)`` as fp32 ``[B, A]`` (``pbx_go_head_probs``): operands as
+    :func:`.eval_heads.go_head_eval` (``g_bf`` bf16, the bf16 mirror of ``Wa``).  ``out``: an fp32 ``[B, A]``
+    tensor or view with unit column stride to write into (only its ``[B, A]`` elements are written)."""
+    B, A = g_bf.shape[0], wa.shape[0]
+    if out is None:
+        out = torch.empty((B, A), dtype=F32, device=g_bf.device)
+    if out.shape != (B, A) or out.dtype != F32 or out.stride(1) != 1 or out.stride(0) < A:
+        raise ValueError(f"go_probs: out must be fp32 [{B}, {A}] with unit column stride")
+    gx = g_bf.contiguous()
+    wab = bf16_of(wa)
+    _lib.call("pbx_go_head_probs", gx.data_ptr(), gx.stride(0), wab.data_ptr(), wab.stride(0),
+              ba.detach().float().contiguous().data_ptr(), out.data_ptr(), out.stride(0), B, A, gx.shape[1],
+              _s(g_bf.device))
+    return out
+
+
+def row_topk(P: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ``k`` largest entries of every row of ``P [B, A]`` fp32 (unit column stride, any row stride; finite
+    values): ``(values [B, k] fp32, indices [B, k] int32)``, descending, ties by ascending index.  Raises
+    ``ValueError`` outside :func:`topk_supported`, before any launch."""
+    if P.dim() != 2 or P.dtype != F32:
+        raise ValueError("row_topk: expected a 2-D fp32 matrix")
+    B, A = P.shape
+    if not topk_supported(A, k):
+        raise ValueError(f"row_topk: k={k} of A={A} columns is outside the kernel's range "
+                         f"(1 <= k <= min({TOPK_MAX_K}, A), A <= {TOPK_MAX_COLS})")
+    if B < 1:
+        raise ValueError("row_topk: empty matrix")
+    if P.stride(1) != 1 or P.stride(0) < A:
+        P = P.contiguous()
+    val = torch.empty((B, k), dtype=F32, device=P.device)
+    idx = torch.empty((B, k), dtype=torch.int32, device=P.device)
+    _lib.call("pbx_row_topk", P.data_ptr(), P.stride(0), B, A, int(k), val.data_ptr(), idx.data_ptr(), _s(P.device))
+    return val, idx
+
+
+def _probs_out(out: Optional[torch.Tensor], store_probs: bool, B: int, L: int, V: int,
+               dev) -> Optional[torch.Tensor]:
+    if not store_probs:
+        return None
+    if out is None:
+        return torch.empty((B, L, V), dtype=F32, device=dev)
+    if out.shape != (B, L, V) or out.dtype != F32 or not out.is_contiguous():
+        raise ValueError(f"local probabilities: out must be a contiguous fp32 [{B}, {L}, {V}] tensor")
+    return out
+
+
+def local_probs_ref(h: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, store_probs: bool = True,
+                    out: Optional[torch.Tensor] = None):
+    """Reference-semantics local head (softmax over the BATCH axis): stage A of the training head
+    (``pbx_local_head3_a``: logits and the folded (M, 1/S) of every (position, token)) and one prediction pass.
+    Returns ``(P [B, L, V] fp32 or None, tok [B, L] int32, pmax [B, L] fp32)``; ``out``: a contiguous fp32
+    ``[B, L, V]`` tensor to write ``P`` into."""
+    dev = h.device
+    st = _s(dev)
+    B, L, C = h.shape
+    V = wo.shape[0]
+    assert C == 128 and h.dtype == torch.bfloat16 and h.is_contiguous()
+    P = _probs_out(out, store_probs, B, L, V, dev)
+    nch = (B + 15) // 16
+    Z = torch.empty((B * L, 32), dtype=F32, device=dev)
+    part = torch.empty((nch, L, 32, 2), dtype=F32, device=dev)
+    ms = torch.empty((L, 32, 2), dtype=F32, device=dev)
+    _lib.call("pbx_local_head3_a", h.data_ptr(), wo.detach().float().contiguous().data_ptr(),
+              bo.detach().float().contiguous().data_ptr(), Z.data_ptr(), part.data_ptr(), ms.data_ptr(),
+              0, B, L, V, st)
+    tok = torch.empty((B, L), dtype=torch.int32, device=dev)
+    pmax = torch.empty((B, L), dtype=F32, device=dev)
+    _lib.call("pbx_local_probs_ref", Z.data_ptr(), ms.data_ptr(), _lib.ptr(P), tok.data_ptr(), pmax.data_ptr(),
+              int(store_probs), B, L, V, st)
+    return P, tok, pmax
+
+
+def local_probs_paper(h: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, store_probs: bool = True,
+                      out: Optional[torch.Tensor] = None):
+    """Paper-semantics local head (softmax over the vocabulary), one launch.  Returns as
+    :func:`local_probs_ref`."""
+    dev = h.device
+    B, L, C = h.shape
+    V = wo.shape[0]
+    assert C == 128 and h.dtype == torch.bfloat16 and h.is_contiguous()
+    P = _probs_out(out, store_probs, B, L, V, dev)
+    tok = torch.empty((B, L), dtype=torch.int32, device=dev)
+    pmax = torch.empty((B, L), dtype=F32, device=dev)
+    _lib.call("pbx_phead_probs", h.data_ptr(), wo.detach().float().contiguous().data_ptr(),
+              bo.detach().float().contiguous().data_ptr(), _lib.ptr(P), tok.data_ptr(), pmax.data_ptr(),
+              int(store_probs), B * L, V, _s(dev))
+    return P, tok, pmax
+
+
+def local_probs(model, h: torch.Tensor, store_probs: bool = True):
+    """The local head of ``model`` (by ``model.semantics``) on ``h [B, L, 128]`` bf16: ``(P or None, tok,
+    pmax)``.  In reference semantics every output depends on the whole batch."""
+    lo = model.pretraining_local_output[0]
+    fn = local_probs_paper if model.semantics == "paper" else local_probs_ref
+    return fn(h, lo.weight, lo.bias, store_probs)
+
+
+def masked_mean_pool(h: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """Mean of ``h [B, L, 128]`` bf16 over the positions with ``tokens [B, L] != 0`` (``<pad>``), fp32
+    ``[B, 128]``, accumulated in fp32 in a fixed order; zeros for a sequence of pads only."""
+    B, L, C = h.shape
+    assert C == 128 and h.dtype == torch.bfloat16 and h.is_contiguous()
+    if tokens.shape != (B, L) or tokens.dtype != torch.int64:
+        raise ValueError("masked_mean_pool: tokens must be int64 [B, L]")
+    out = torch.empty((B, C), dtype=F32, device=h.device)
+    _lib.call("pbx_masked_mean_pool", h.data_ptr(), tokens.contiguous().data_ptr(), out.data_ptr(), B, L,
+              _s(h.device))
+    return out
