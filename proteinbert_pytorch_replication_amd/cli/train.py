@@ -126,8 +126,18 @@ def pretrain_main(argv: Optional[List[str]] = None) -> dict:
                              f"{cfg.data.source!r}")
         else:
             eval_loader = make_loader(cfg.eval.path, cfg.data.seed)
-    opt = torch.optim.Adam(model.parameters(), lr=cfg.optim.lr, betas=cfg.optim.betas, eps=cfg.optim.eps,
-                           weight_decay=cfg.optim.weight_decay)
+    if cfg.optim.decoupled_weight_decay or (cfg.optim.no_decay_norm_bias and cfg.optim.weight_decay):
+        # AdamW and / or weight decay that skips biases and LayerNorm affines: parameter groups, which
+        # pretrain() turns into one FusedAdam over the model's arena
+        from ..train.optim import param_groups_for
+        groups = param_groups_for(model, cfg.optim.lr, cfg.optim.weight_decay,
+                                  no_decay=("bias", "norm") if cfg.optim.no_decay_norm_bias else ())
+        cls = torch.optim.AdamW if cfg.optim.decoupled_weight_decay else torch.optim.Adam
+        opt = cls(groups, lr=cfg.optim.lr, betas=cfg.optim.betas, eps=cfg.optim.eps,
+                  weight_decay=cfg.optim.weight_decay)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=cfg.optim.lr, betas=cfg.optim.betas, eps=cfg.optim.eps,
+                               weight_decay=cfg.optim.weight_decay)
     from ..train.pretrain import pretrain
     res = pretrain(model, loader, opt, max_batch_iterations=cfg.train.max_batch_iterations,
                    save_path=cfg.train.save_path, nb_iterations_checkpoint=cfg.train.nb_iterations_checkpoint,
@@ -175,6 +185,11 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--unfreeze", action="store_true", help="train the encoder as well")
+    ap.add_argument("--encoder-lr", type=float, default=None,
+                    help="with --unfreeze: the encoder's learning rate (default: --lr, one parameter group)")
+    ap.add_argument("--weight-decay", type=float, default=0.0,
+                    help="weight decay on everything but biases and LayerNorm affines")
+    ap.add_argument("--decoupled", action="store_true", help="AdamW (decoupled weight decay) instead of Adam")
     ap.add_argument("--synthetic-samples", type=int, default=2048)
     a = ap.parse_args(argv)
     cfg = _cfg(a)
@@ -208,9 +223,24 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
     dl = DataLoader(train_ds, batch_size=B, sampler=ShardedSampler(len(train_ds), info.rank, info.world_size),
                     drop_last=True)
     tl = DataLoader(test_ds, batch_size=B) if test_ds is not None else None
-    from ..train.optim import FusedAdam
-    params = [p for p in model.parameters() if p.requires_grad]
-    opt = FusedAdam(params, lr=a.lr)
+    from ..train.optim import FusedAdam, make_optimizer, param_groups_for
+    enc_lr = a.lr if a.encoder_lr is None else a.encoder_lr
+    if a.unfreeze and enc_lr != a.lr:
+        # the pretrained encoder and the fresh head as two (with weight decay: up to four) groups of one FusedAdam
+        if a.lr == 0:
+            raise ValueError("--encoder-lr needs a non-zero --lr (it is applied as a factor on it)")
+        groups = param_groups_for(model, a.lr, a.weight_decay, lr_scale={"encoder.": enc_lr / a.lr})
+        for g in groups:
+            if g["lr"] != a.lr:
+                g["lr"] = enc_lr            # the rate as given, not lr * (encoder_lr / lr)
+        opt = make_optimizer(model, lr=a.lr, weight_decay=a.weight_decay, groups=groups,
+                             decoupled_weight_decay=a.decoupled)
+    elif a.weight_decay or a.decoupled:
+        opt = make_optimizer(model, lr=a.lr, weight_decay=a.weight_decay, groups=param_groups_for(
+            model, a.lr, a.weight_decay), decoupled_weight_decay=a.decoupled)
+    else:
+        params = [p for p in model.parameters() if p.requires_grad]
+        opt = FusedAdam(params, lr=a.lr)
     ddp = None
     if info.distributed:
         from ..parallel.ddp import BucketedAllReduce
@@ -220,6 +250,7 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
     from ..train.finetune import finetune, token_accuracy
     res = finetune(model, dl, opt, epochs=a.epochs, test_dataloader=tl, metrics={"accuracy": token_accuracy()},
                    device=dev, ddp=ddp, log=print)
+    res["optimizer"] = opt
     if info.is_main:
         os.makedirs(cfg.train.save_path, exist_ok=True)
         path = os.path.join(cfg.train.save_path, "proteinbert_finetuned_head.pt")

@@ -64,6 +64,8 @@ class OptimConfig:
     betas: tuple = (0.9, 0.999)
     eps: float = 1e-8
     weight_decay: float = 0.0
+    decoupled_weight_decay: bool = False    # AdamW's rule (p *= 1 - lr * wd) instead of Adam's wd * p gradient term
+    no_decay_norm_bias: bool = False    # weight_decay skips biases and LayerNorm affines (a second parameter group)
     warmup_duration: int = 10000        # utils.py:229
     plateau_patience: int = 25          # utils.py:228
     plateau_factor: float = 0.1

@@ -78,6 +78,104 @@ PBX_EXPORT int pbx_adam_flat(float* p, const float* g, float* m, float* v, void*
   return pbx_launch_status();
 }
 
+// ---- parameter groups ------------------------------------------------------------------------
+// Every arena segment starts on a 64-element boundary, so one byte per 64-element block names the
+// block's group (block_group, relative to p) and the update stays one launch for any number of
+// groups: +1/64 byte per element on top of the ~30 the update moves.  Each workgroup resolves the
+// groups' blocks once (device bias corrections from each group's own betas) into LDS; a lane
+// reads the block of its group from there.  A wave's 64 lanes cover four 64-element blocks per
+// pass, i.e. up to four groups.  Bit k of decoupled_mask: group k decays its weights AdamW's way.
+#define PBX_ADAM_MAX_GROUPS 16
+
+// torch.optim.AdamW: p *= 1 - lr * wd first, no wd * p term in the gradient
+__device__ __forceinline__ void adam_one_decoupled(float& p, float g, float& m, float& v, const AdamHParams& h) {
+  p *= 1.0f - h.lr * h.weight_decay;
+  g = g * h.grad_scale;
+  m = h.beta1 * m + (1.0f - h.beta1) * g;
+  v = h.beta2 * v + (1.0f - h.beta2) * g * g;
+  const float denom = sqrtf(v) / h.bias_correction2_sqrt + h.eps;
+  p -= (h.lr / h.bias_correction1) * (m / denom);
+}
+
+__global__ void __launch_bounds__(256) adam_flat_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               unsigned short* __restrict__ shadow, int64_t n,
+                                                               const AdamHParams* __restrict__ hp, int n_groups,
+                                                               unsigned decoupled_mask,
+                                                               const unsigned char* __restrict__ block_group,
+                                                               const int* __restrict__ skip,
+                                                               const float* __restrict__ step_dev) {
+  if (skip != nullptr && *skip != 0) return;
+  __shared__ AdamHParams hs[PBX_ADAM_MAX_GROUPS];
+  if ((int)threadIdx.x < n_groups) {
+    AdamHParams h = hp[threadIdx.x];
+    if (step_dev != nullptr) {
+      const float t = *step_dev;
+      h.bias_correction1 = 1.0f - powf(h.beta1, t);
+      h.bias_correction2_sqrt = sqrtf(1.0f - powf(h.beta2, t));
+    }
+    hs[threadIdx.x] = h;
+  }
+  __syncthreads();
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    // 16 float4 per 64-element block; the mask keeps a bad table entry inside hs
+    const unsigned gi = block_group[i >> 4] & (PBX_ADAM_MAX_GROUPS - 1);
+    const AdamHParams h = hs[gi];
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 mm = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    if ((decoupled_mask >> gi) & 1u) {
+      adam_one_decoupled(pp.x, gg.x, mm.x, vv.x, h);
+      adam_one_decoupled(pp.y, gg.y, mm.y, vv.y, h);
+      adam_one_decoupled(pp.z, gg.z, mm.z, vv.z, h);
+      adam_one_decoupled(pp.w, gg.w, mm.w, vv.w, h);
+    } else {
+      adam_one(pp.x, gg.x, mm.x, vv.x, h);
+      adam_one(pp.y, gg.y, mm.y, vv.y, h);
+      adam_one(pp.z, gg.z, mm.z, vv.z, h);
+      adam_one(pp.w, gg.w, mm.w, vv.w, h);
+    }
+    reinterpret_cast<float4*>(p)[i] = pp;
+    reinterpret_cast<float4*>(m)[i] = mm;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    if (shadow != nullptr) {
+      ushort4 s;
+      s.x = f2bf(pp.x); s.y = f2bf(pp.y); s.z = f2bf(pp.z); s.w = f2bf(pp.w);
+      reinterpret_cast<ushort4*>(shadow)[i] = s;
+    }
+  }
+  // tail
+  const int64_t t = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n && blockIdx.x * blockDim.x + threadIdx.x < 4) {
+    const unsigned gi = block_group[t >> 6] & (PBX_ADAM_MAX_GROUPS - 1);
+    const AdamHParams h = hs[gi];
+    float pp = p[t], mm = m[t], vv = v[t];
+    if ((decoupled_mask >> gi) & 1u) adam_one_decoupled(pp, g[t], mm, vv, h);
+    else adam_one(pp, g[t], mm, vv, h);
+    p[t] = pp; m[t] = mm; v[t] = vv;
+    if (shadow != nullptr) shadow[t] = f2bf(pp);
+  }
+}
+
+// hparams: [n_groups][8] float32 (AdamHParams per group); block_group: uint8[ceil(n / 64)]
+PBX_EXPORT int pbx_adam_flat_groups(float* p, const float* g, float* m, float* v, void* shadow, int64_t n,
+                                    const void* hparams, int n_groups, int decoupled_mask,
+                                    const void* block_group, const int* skip, const float* step_dev,
+                                    hipStream_t stream) {
+  if (n_groups < 1 || n_groups > PBX_ADAM_MAX_GROUPS) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  int64_t blocks = ((n >> 2) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adam_flat_groups_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v,
+                     (unsigned short*)shadow, n, (const AdamHParams*)hparams, n_groups, (unsigned)decoupled_mask,
+                     (const unsigned char*)block_group, skip, step_dev);
+  return pbx_launch_status();
+}
+
 // ---- global L2 norm of a flat buffer (clip_grad_norm_) --------------------------
 // Two passes in one launch sequence: per-block partial sums of squares -> out[blocks],
 // then a single-block reduce into out_total[0].  Deterministic (fixed tree).

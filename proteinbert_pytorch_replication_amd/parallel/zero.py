@@ -6,7 +6,8 @@ parameter arena (``train/arena.py``) instead of all of it. ``step()`` is:
 
 1. reduce-scatter of the flat gradient (SUM; the 1/world mean is folded into the Adam launch's
    ``grad_scale``) — each rank receives only its slice, i.e. half the bytes of an all-reduce;
-2. the fused Adam launch (``pbx_adam_flat``, ``csrc/optim.hip``) on that slice only;
+2. the fused Adam launch (``pbx_adam_flat``, or ``pbx_adam_flat_groups`` with parameter groups,
+   ``csrc/optim.hip``) on that slice only;
 3. all-gather of the updated fp32 slices back into every rank's arena (+ bf16 mirror refresh).
 
 Reduce-scatter + all-gather move the same bytes as one ring all-reduce over xGMI, so step time is
@@ -24,12 +25,13 @@ import torch
 import torch.distributed as dist
 
 from ..train.arena import ALIGN
-from ..train.optim import FusedAdam, _hip_ok, adam_update_host, skip_requested
+from ..train.optim import FusedAdam, _hip_ok, skip_requested
 
 
 class ZeroFusedAdam(FusedAdam):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, process_group=None, **kw):
+        # params: a parameter list, the arena, or group dicts (then with arena=...), as FusedAdam takes them
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -118,11 +120,10 @@ class ZeroFusedAdam(FusedAdam):
                 self.prepare()
                 self._step_dev.add_(1.0)
                 sh = self.shadow[self.lo:self.hi] if self.shadow is not None else None
-                _lib.call("pbx_adam_flat", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _lib.ptr(sh), n,
-                          self._hp_dev.data_ptr(), _lib.ptr(self.skip_flag), self._step_dev.data_ptr(),
-                          _lib.stream_ptr(a.data.device))
+                # shard bounds are multiples of ALIGN: the grouped launch reads the block table from lo / ALIGN
+                self._launch(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _lib.ptr(sh), self.lo, n)
             elif not skip_requested(self.skip_flag):
-                adam_update_host(self, p, g, m, v)
+                self._update_host(self.lo, self.hi, p, g, m, v)
         self._all_gather()
         return loss
 

@@ -36,7 +36,7 @@ from ..parallel import dist as pdist
 from ..parallel.ddp import BucketedAllReduce
 from .checkpoint import (CheckpointWriter, build_checkpoint, checkpoint_name, latest_checkpoint, load_checkpoint,
                          rng_state, save_final_model, set_rng_state)
-from .optim import FusedAdam
+from .optim import MAX_GROUPS, FusedAdam
 from .schedulers import WarmupThenPlateau
 from .step import PretrainStep
 from ..utils.metrics import MetricsWriter
@@ -55,16 +55,37 @@ def _loader_state(loader) -> Dict[str, Any]:
 
 
 def _maybe_fuse_optimizer(model, optimizer) -> torch.optim.Optimizer:
-    if isinstance(optimizer, FusedAdam) or type(optimizer) is not torch.optim.Adam:
+    """``torch.optim.Adam`` / ``AdamW`` with any number of groups (at most FusedAdam's 16) becomes the fused
+    optimizer with the same groups; ``amsgrad`` and ``maximize`` stay with PyTorch."""
+    if isinstance(optimizer, FusedAdam) or type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW):
         return optimizer
     g = optimizer.param_groups
-    if len(g) != 1 or g[0].get("amsgrad") or g[0].get("maximize"):
+    if len(g) > MAX_GROUPS or any(x.get("amsgrad") or x.get("maximize") for x in g):
         return optimizer
-    fused = FusedAdam(g[0]["params"], lr=g[0]["lr"], betas=g[0]["betas"], eps=g[0]["eps"],
-                      weight_decay=g[0]["weight_decay"])
+    if len(g) == 1 and not g[0].get("decoupled_weight_decay"):
+        fused = FusedAdam(g[0]["params"], lr=g[0]["lr"], betas=g[0]["betas"], eps=g[0]["eps"],
+                          weight_decay=g[0]["weight_decay"])
+    else:
+        # the arena is laid out from the model's own parameter order, whatever the grouping (DP buckets)
+        fused = FusedAdam(_fused_groups(g), arena=_model_arena(model, g))
     if optimizer.state:
         fused.load_state_dict(optimizer.state_dict())
     return fused
+
+
+def _fused_groups(groups):
+    return [dict(params=list(x["params"]), lr=x["lr"], betas=tuple(x["betas"]), eps=x["eps"],
+                 weight_decay=x["weight_decay"], decoupled_weight_decay=bool(x.get("decoupled_weight_decay", False)))
+            for x in groups]
+
+
+def _model_arena(model, groups):
+    from .arena import FlatArena
+    grouped = {id(p) for x in groups for p in x["params"] if p.requires_grad}
+    ordered = [p for p in model.parameters() if id(p) in grouped]
+    if len(ordered) != len(grouped):          # parameters from outside the model: keep the groups' own order
+        ordered = [p for x in groups for p in x["params"]]
+    return FlatArena(ordered)
 
 
 def _evaluate(model, loader, max_batches, device, compute_dtype, info, step, metrics, tb) -> Dict[str, Any]:
@@ -119,9 +140,13 @@ def pretrain(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
             raise ValueError("data-parallel pretrain needs FusedAdam (flat gradient arena)")
         if zero_optimizer and not isinstance(optimizer, ZeroFusedAdam):
             # ZeRO-1: Adam moments sharded over the DP ranks (parallel/zero.py); reduce-scatter at step()
-            g = optimizer.param_groups[0]
-            zopt = ZeroFusedAdam(optimizer.arena, lr=g["lr"], betas=g["betas"], eps=g["eps"],
-                                 weight_decay=g["weight_decay"])
+            gs = optimizer.param_groups
+            if len(gs) == 1 and not gs[0].get("decoupled_weight_decay"):
+                g = gs[0]
+                zopt = ZeroFusedAdam(optimizer.arena, lr=g["lr"], betas=g["betas"], eps=g["eps"],
+                                     weight_decay=g["weight_decay"])
+            else:
+                zopt = ZeroFusedAdam(_fused_groups(gs), arena=optimizer.arena)
             if optimizer.step_count:
                 zopt.load_state_dict(optimizer.state_dict())
             optimizer = zopt
