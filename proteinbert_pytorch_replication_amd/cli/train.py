@@ -9,8 +9,12 @@ store or a directory of them, read by the native loader) or ``dataframe`` (``dat
 with ``seq`` and space-separated ``annotations`` index columns).  The reference's own driver is
 ``dummy_tests.py`` (see :mod:`.dummy_tests`).
 
-``finetune``: frozen (or full) encoder + per-residue head on synthetic secondary-structure data or a
-CSV with ``seq`` and ``labels`` (one class character per residue, classes given by ``--classes``).
+``finetune``: frozen (or full) encoder + a task head, on synthetic data or CSVs.  ``--task residue`` (the
+default): per-residue classes, CSV columns ``seq`` and ``labels`` (one class character per residue, classes
+given by ``--classes``).  ``--task sequence``: per-protein classes, columns ``seq`` and ``label`` (an integer in
+``0..n-1``, ``--n-classes n``), accuracy.  ``--task regression``: columns ``seq`` and ``label`` (a float), MSE
+loss and the test set's Spearman correlation per epoch.  ``--hidden all`` puts the head on every block's hidden
+state instead of the last block's (:mod:`..models.finetune`).
 """
 from __future__ import annotations
 
@@ -24,7 +28,8 @@ import torch
 
 from ..config import RunConfig, apply_overrides, get_preset, load_yaml, PRESETS
 from ..data import SyntheticUniRefGO, CorruptionParams
-from ..models import ProteinBERT, ProteinBERTForTokenClassification, build_model
+from ..models import (ProteinBERT, ProteinBERTForSequenceClassification, ProteinBERTForTokenClassification,
+                      build_model)
 from ..utils import determinism
 from ..parallel import dist as pdist
 
@@ -175,8 +180,55 @@ def _ss_csv(path: str, L: int, classes: str):
     return torch.utils.data.TensorDataset(torch.tensor(toks), torch.tensor(labs))
 
 
+def _seq_csv(path: str, L: int, regression: bool, n_classes: int):
+    """``seq,label`` CSV -> (tokens [N, L], labels [N]): float targets (regression) or classes ``0..n-1``."""
+    import pandas as pd
+    from ..data.vocab import create_amino_acid_vocab, SOS_ID, EOS_ID
+    v = create_amino_acid_vocab()
+    df = pd.read_csv(path)
+    toks = []
+    for seq in df["seq"]:
+        t = [SOS_ID] + list(v.encode(str(seq)[: L - 2])) + [EOS_ID]
+        toks.append(t + [0] * (L - len(t)))
+    if regression:
+        labs = torch.tensor([float(x) for x in df["label"]], dtype=torch.float32)
+    else:
+        labs = torch.tensor([int(x) for x in df["label"]], dtype=torch.int64)
+        if len(labs) and (int(labs.min()) < 0 or int(labs.max()) >= n_classes):
+            raise ValueError(f"{path}: labels must lie in 0..{n_classes - 1} (--n-classes {n_classes})")
+    return torch.utils.data.TensorDataset(torch.tensor(toks), labs)
+
+
+FINETUNE_TASKS = ("residue", "sequence", "regression")
+
+
+def build_finetune_model(enc: ProteinBERT, meta: dict, freeze_encoder: bool = True):
+    """The head class a saved head file's ``meta`` describes (:func:`load_finetuned_head`)."""
+    if meta["task"] == "residue":
+        return ProteinBERTForTokenClassification(enc, n_classes=meta["n_classes"], freeze_encoder=freeze_encoder,
+                                                 use_global=meta["use_global"], hidden=meta["hidden"])
+    return ProteinBERTForSequenceClassification(enc, n_classes=meta["n_classes"], freeze_encoder=freeze_encoder,
+                                                hidden=meta["hidden"])
+
+
+def load_finetuned_head(path: str, enc: ProteinBERT, freeze_encoder: bool = True):
+    """Rebuild the fine-tuned model of a ``proteinbert_finetuned_head.pt`` around ``enc``.  The file's ``"meta"``
+    entry names the task and head form; a file without it is a ``hidden="last"`` per-residue head."""
+    state = dict(torch.load(path, map_location="cpu"))
+    meta = state.pop("meta", None)
+    if meta is None:
+        meta = {"task": "residue", "hidden": "last", "n_classes": state["head.weight"].shape[0], "classes": None,
+                "use_global": "global_head.weight" in state}
+    model = build_finetune_model(enc, meta, freeze_encoder)
+    missing, unexpected = model.load_state_dict(state, strict=False)
+    if unexpected or any(not k.startswith("encoder.") for k in missing):
+        raise ValueError(f"{path}: head does not fit meta {meta}: missing "
+                         f"{[k for k in missing if not k.startswith('encoder.')]}, unexpected {unexpected}")
+    return model, meta
+
+
 def finetune_main(argv: Optional[List[str]] = None) -> dict:
-    ap = argparse.ArgumentParser(description="ProteinBERT fine-tuning: per-residue classification head")
+    ap = argparse.ArgumentParser(description="ProteinBERT fine-tuning: per-residue / per-protein task heads")
     _common(ap)
     ap.add_argument("--pretrained", default=None, help="pretrained model/checkpoint (.pt) to start from")
     ap.add_argument("--train-csv", default=None)
@@ -191,10 +243,17 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
                     help="weight decay on everything but biases and LayerNorm affines")
     ap.add_argument("--decoupled", action="store_true", help="AdamW (decoupled weight decay) instead of Adam")
     ap.add_argument("--synthetic-samples", type=int, default=2048)
+    ap.add_argument("--task", default="residue", choices=FINETUNE_TASKS,
+                    help="residue: per-residue classes; sequence: per-protein classes; regression: per-protein value")
+    ap.add_argument("--hidden", default="last", choices=("last", "all"),
+                    help="head input: the last block's hidden state, or every block's, concatenated")
+    ap.add_argument("--n-classes", type=int, default=2, help="--task sequence: number of classes")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(format="%(asctime)s [%(levelname)s]: %(message)s", level=logging.INFO)
     info = pdist.init_distributed(backend=cfg.dist.backend)
+    if a.task == "sequence" and a.n_classes < 2:
+        raise ValueError("--task sequence needs --n-classes >= 2")
     if cfg.kernel.deterministic:
         determinism.enable()
     if cfg.kernel.gelu != "fitted":
@@ -208,11 +267,21 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
     else:
         enc = build_model(cfg.model, device=dev, backend=determinism.backend_for(cfg.kernel.backend, cfg.model))
     L = enc.config["sequences_length"]
-    model = ProteinBERTForTokenClassification(enc, n_classes=len(a.classes), freeze_encoder=not a.unfreeze)
+    n_classes = {"residue": len(a.classes), "sequence": a.n_classes, "regression": 1}[a.task]
+    meta = {"task": a.task, "hidden": a.hidden, "n_classes": n_classes,
+            "classes": a.classes if a.task == "residue" else None, "use_global": a.task == "residue"}
+    model = build_finetune_model(enc, meta, freeze_encoder=not a.unfreeze)
     from torch.utils.data import DataLoader
-    from ..data.synthetic import SyntheticSecondaryStructure
+    from ..data.synthetic import SyntheticSecondaryStructure, SyntheticSequenceTask
     from ..parallel.sampler import ShardedSampler
-    if a.train_csv:
+    if a.task != "residue":
+        if a.train_csv:
+            train_ds = _seq_csv(a.train_csv, L, a.task == "regression", n_classes)
+            test_ds = _seq_csv(a.test_csv, L, a.task == "regression", n_classes) if a.test_csv else None
+        else:
+            train_ds = SyntheticSequenceTask(a.synthetic_samples, L, n_classes, seed=cfg.train.seed)
+            test_ds = SyntheticSequenceTask(max(64, a.synthetic_samples // 8), L, n_classes, seed=cfg.train.seed + 1)
+    elif a.train_csv:
         train_ds = _ss_csv(a.train_csv, L, a.classes)
         test_ds = _ss_csv(a.test_csv, L, a.classes) if a.test_csv else None
     else:
@@ -247,13 +316,27 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
         ddp = BucketedAllReduce(opt.arena, bucket_mb=cfg.dist.bucket_mb)
         ddp.broadcast_parameters(model)
         opt.grad_scale = 1.0 / info.world_size
-    from ..train.finetune import finetune, token_accuracy
-    res = finetune(model, dl, opt, epochs=a.epochs, test_dataloader=tl, metrics={"accuracy": token_accuracy()},
-                   device=dev, ddp=ddp, log=print)
+    from ..train.finetune import finetune, regression_loss, sequence_accuracy, spearman, token_accuracy
+    if a.task == "residue":
+        task_args = dict(metrics={"accuracy": token_accuracy()})
+    elif a.task == "sequence":
+        task_args = dict(metrics={"accuracy": sequence_accuracy()}, loss_fn=torch.nn.CrossEntropyLoss())
+    else:
+        # Spearman is a statistic of the whole test set, computed once per epoch, not a mean over batches
+        task_args = dict(metrics={}, loss_fn=regression_loss(), epoch_metrics={"spearman": spearman})
+    res = finetune(model, dl, opt, epochs=a.epochs, test_dataloader=tl, device=dev, ddp=ddp, log=print, **task_args)
     res["optimizer"] = opt
+    res["meta"] = meta
+    res["model"] = model
     if info.is_main:
         os.makedirs(cfg.train.save_path, exist_ok=True)
         path = os.path.join(cfg.train.save_path, "proteinbert_finetuned_head.pt")
-        torch.save({k: v for k, v in model.state_dict().items() if not k.startswith("encoder.")}, path)
+        head = {k: v for k, v in model.state_dict().items() if not k.startswith("encoder.")}
+        # the default form keeps the file it always had (tensors only), which load_finetuned_head reads as
+        # task="residue", hidden="last"; every other form says what it is
+        if (a.task, a.hidden) != ("residue", "last"):
+            head["meta"] = meta
+        torch.save(head, path)
+        res["head"] = path
         print(json.dumps({"train_loss": res["train_loss"], "test_metrics": res["test_metrics"], "head": path}))
     return res

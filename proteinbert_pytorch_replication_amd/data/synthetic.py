@@ -194,3 +194,31 @@ class SyntheticSecondaryStructure(torch.utils.data.Dataset):
 
     def __getitem__(self, i: int):
         return self.tokens[i], self.labels[i]
+
+
+class SyntheticSequenceTask(torch.utils.data.Dataset):
+    """Per-protein labelled synthetic proteins for the per-protein fine-tuning tasks (classes or regression).
+
+    Item: ``(tokens int64 [L], label)``.  The label is a function of the sequence's amino-acid composition: the
+    fraction ``f`` of residues whose token id is even.  ``n_classes >= 2``: ``f``'s quantile bin among the
+    ``n`` samples (int64 in ``0..n_classes-1``, balanced); ``n_classes == 1``: the regression target
+    ``(f - 0.5) * 8`` (float32, roughly unit scale)."""
+
+    def __init__(self, n: int, seq_len: int, n_classes: int = 2, min_length: int = 16,
+                 max_length: Optional[int] = None, seed: int = 0):
+        ss = SyntheticSecondaryStructure(n, seq_len, 2, min_length, max_length, seed)
+        tok = ss.tokens
+        res = tok > EOS_ID
+        f = ((tok % 2 == 0) & res).sum(1).float() / res.sum(1).clamp_min(1).float()
+        if n_classes == 1:
+            lab = (f - 0.5) * 8.0
+        else:
+            rank = torch.argsort(torch.argsort(f, stable=True), stable=True)
+            lab = (rank * n_classes // max(1, n)).clamp_max(n_classes - 1)
+        self.tokens, self.labels = tok, lab
+
+    def __len__(self) -> int:
+        return self.tokens.shape[0]
+
+    def __getitem__(self, i: int):
+        return self.tokens[i], self.labels[i]

@@ -14,10 +14,16 @@ frozen-encoder step costs one forward of the fused HIP encoder plus the tiny hea
 ``freeze_encoder=False`` gradients flow through the fused HIP backward as in pretraining.
 Inputs: a token tensor ``[B, L]`` (annotations default to zeros, i.e. "no GO prior") or the
 pretraining dict ``{"local": tokens, "global": annotations}``.
+
+``hidden="last"`` (the default) reads the last block's output.  ``hidden="all"`` puts the task layer on the
+concatenation of every block's hidden state, block 0 first: the local states ``h_i`` for the per-residue
+head (``Linear(num_blocks * local_dim, K)``; on a GPU one streaming HIP launch over the ``num_blocks`` row
+sources, :class:`..ops.finetune_head.MultiTokenHeadFn`), the global states ``g_i`` for the per-protein head
+(``Linear(num_blocks * global_dim, n_classes)``; ``n_classes=1`` is the regression form, output ``[B, 1]``).
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple, Union
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -35,19 +41,28 @@ def _split_inputs(model: ProteinBERT, x: Inputs) -> Tuple[torch.Tensor, torch.Te
     return x, torch.zeros((x.shape[0], A), dtype=torch.float32, device=x.device)
 
 
-def encode(model: ProteinBERT, tokens: torch.Tensor, ann: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Encoder output ``h [B, L, C]``, ``g [B, G]`` on the model's backend (fused HIP on a GPU)."""
+HIDDEN = ("last", "all")
+
+
+def encode(model: ProteinBERT, tokens: torch.Tensor, ann: torch.Tensor,
+           tap: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Encoder output ``h [B, L, C]``, ``g [B, G]`` on the model's backend (fused HIP on a GPU).
+    ``tap``: called as ``tap(i, h_i, g_i)`` after block ``i`` with that block's outputs."""
     if model.resolved_backend(tokens.device) == "hip":
         from ..ops.fused_model import fused_encode
-        return fused_encode(model, tokens, ann.float())
-    return model.encode_torch(tokens, ann.float())
+        return fused_encode(model, tokens, ann.float(), tap=tap)
+    return model.encode_torch(tokens, ann.float(), tap=tap)
 
 
 class _FinetuneBase(nn.Module):
-    def __init__(self, encoder: ProteinBERT, freeze_encoder: bool = True):
+    def __init__(self, encoder: ProteinBERT, freeze_encoder: bool = True, hidden: str = "last"):
         super().__init__()
+        if hidden not in HIDDEN:
+            raise ValueError(f"hidden={hidden!r}: expected one of {HIDDEN}")
         self.encoder = encoder
         self.freeze_encoder = freeze_encoder
+        self.hidden = hidden
+        self.num_blocks = len(encoder.proteinBERT_blocks)
         if freeze_encoder:
             for p in encoder.parameters():
                 p.requires_grad_(False)
@@ -60,6 +75,26 @@ class _FinetuneBase(nn.Module):
             return h.detach(), g.detach()
         return encode(self.encoder, tokens, ann)
 
+    def _encode_all(self, x: Inputs) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+        """Every block's ``(h_i, g_i)``, block 0 first.  The lists hold a reference to each block's output until
+        the head has consumed it: both local tracks allocate a fresh output per block (``ops/local_track.py``
+        ``h2``, ``ops/paper_track.py`` ``h2``; no buffer is recycled by a later block, with or without
+        ``no_grad``), so a held reference is all that keeps the rows alive."""
+        tokens, ann = _split_inputs(self.encoder, x)
+        hs: List[torch.Tensor] = []
+        gs: List[torch.Tensor] = []
+
+        def tap(i, h_i, g_i):
+            hs.append(h_i)
+            gs.append(g_i)
+
+        if self.freeze_encoder:
+            with torch.no_grad():
+                encode(self.encoder, tokens, ann, tap=tap)
+            return [h.detach() for h in hs], [g.detach() for g in gs]
+        encode(self.encoder, tokens, ann, tap=tap)
+        return hs, gs
+
     def train(self, mode: bool = True):
         super().train(mode)
         if self.freeze_encoder:
@@ -69,18 +104,37 @@ class _FinetuneBase(nn.Module):
 
 class ProteinBERTForTokenClassification(_FinetuneBase):
     def __init__(self, encoder: ProteinBERT, n_classes: int = 8, freeze_encoder: bool = True,
-                 use_global: bool = True, dropout: float = 0.0):
-        super().__init__(encoder, freeze_encoder)
+                 use_global: bool = True, dropout: float = 0.0, hidden: str = "last"):
+        super().__init__(encoder, freeze_encoder, hidden)
         C, G = encoder.config["local_dim"], encoder.config["global_dim"]
         dev = encoder.local_embedding.weight.device
         self.use_global = use_global
         self.n_classes = n_classes
         self.dropout = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
-        self.head = nn.Linear(C, n_classes, device=dev)
+        nb = self.num_blocks if hidden == "all" else 1
+        self.head = nn.Linear(nb * C, n_classes, device=dev)
         # per-residue logits = W_l h + (W_g g) broadcast over L  ==  Linear(concat(h, g))
-        self.global_head = nn.Linear(G, n_classes, bias=False, device=dev) if use_global else None
+        self.global_head = nn.Linear(nb * G, n_classes, bias=False, device=dev) if use_global else None
+
+    def _forward_all(self, x: Inputs) -> torch.Tensor:
+        hs, gs = self._encode_all(x)
+        gterm = None
+        if self.global_head is not None:
+            gterm = self.global_head(torch.cat([g.float() for g in gs], dim=-1))          # [B, K]
+        from ..ops import finetune_head
+        if finetune_head.supported_multi(hs, self.n_classes) and isinstance(self.dropout, nn.Identity):
+            # one streaming pass over the num_blocks row sources: the concatenation is never written
+            logits = finetune_head.MultiTokenHeadFn.apply(*hs, self.head.weight, self.head.bias, gterm)
+        else:
+            feats = self.dropout(torch.cat([h.float() for h in hs], dim=-1))
+            logits = F.linear(feats, self.head.weight, self.head.bias)                      # [B, L, K]
+            if gterm is not None:
+                logits = logits + gterm.unsqueeze(1)
+        return logits.permute(0, 2, 1)                                                   # [B, K, L]
 
     def forward(self, x: Inputs) -> torch.Tensor:
+        if self.hidden == "all":
+            return self._forward_all(x)
         h, g = self._encode(x)
         from ..ops import finetune_head
         if finetune_head.supported(h, self.n_classes) and isinstance(self.dropout, nn.Identity):
@@ -96,13 +150,17 @@ class ProteinBERTForTokenClassification(_FinetuneBase):
 
 class ProteinBERTForSequenceClassification(_FinetuneBase):
     def __init__(self, encoder: ProteinBERT, n_classes: int = 2, freeze_encoder: bool = True,
-                 dropout: float = 0.0):
-        super().__init__(encoder, freeze_encoder)
+                 dropout: float = 0.0, hidden: str = "last"):
+        super().__init__(encoder, freeze_encoder, hidden)
         G = encoder.config["global_dim"]
         dev = encoder.local_embedding.weight.device
+        self.n_classes = n_classes
         self.dropout = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
-        self.head = nn.Linear(G, n_classes, device=dev)
+        self.head = nn.Linear((self.num_blocks if hidden == "all" else 1) * G, n_classes, device=dev)
 
     def forward(self, x: Inputs) -> torch.Tensor:
+        if self.hidden == "all":
+            _, gs = self._encode_all(x)
+            return self.head(self.dropout(torch.cat([g.float() for g in gs], dim=-1)))
         _, g = self._encode(x)
         return self.head(self.dropout(g.float()))

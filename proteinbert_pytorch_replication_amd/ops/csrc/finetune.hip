@@ -114,7 +114,235 @@ int token_head_fwd_launch(const void* h, const float* W, const float* b, float* 
                      (const bf16_t*)h, W, b, out, M);
   return pbx_launch_status();
 }
+
+// ---- heads over every block's hidden state (hidden="all"): nb <= 8 sources of [M][128] bf16 ----
+// The source addresses travel in the kernel's by-value argument block (no device-side table, no copy).
+constexpr int MAXSRC = 8;
+struct MultiSrc {
+  const bf16_t* p[MAXSRC];
+};
+
+//   out[m][k] = b[k] + sum_i sum_c h_i[m][c] W[k][i * 128 + c]  (+ gterm[m / L][k])
+// token_head_fwd_kernel's scheme with the block walk inside the workgroup: a thread keeps its row's K
+// accumulators in registers across the nb blocks (blocks ascending, channels ascending inside a block: for
+// nb = 1 and no gterm the FMA sequence is token_head_fwd_kernel's), gterm is added last and out is written
+// once.  Every block's 256 rows and [K][128] weight slice pass through one 64 KiB + K * 512 B LDS image, so two
+// workgroups stay resident per CU; the next block's rows are fetched into registers (16 x 16 B per thread)
+// before the FMAs over the current image and stored after them, which hides the fetch behind the compute.
+// (A second LDS image instead of the registers leaves one workgroup per CU and ran 1.8x slower at the cfg-5
+// shape; no prefetch at all 1.1x slower: profiles/r15/finetune_hidden_heads.txt.)  Rows >= M are neither read
+// nor written.
+template <int K>
+__global__ void __launch_bounds__(256) token_head_multi_fwd_kernel(const MultiSrc src, const int nb,
+                                                                   const float* __restrict__ W,
+                                                                   const float* __restrict__ b,
+                                                                   const float* __restrict__ gterm,
+                                                                   float* __restrict__ out, long M, int L) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 256 rows x 256 B
+  __shared__ float ws[K * CH];
+  const long m0 = (long)blockIdx.x * 256;
+  const int n = (int)min((long)256, M - m0);
+  const int row = threadIdx.x;
+  const int ldw = nb * CH;
+  float acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = b[k];
+  uint4 pre[16];                             // chunk idx = tid + 256 j of block i: row idx >> 4, 16-B chunk idx & 15
+  auto fetch = [&](int i) {
+    const bf16_t* __restrict__ h = src.p[i];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      pre[j] = (idx >> 4) < n ? *reinterpret_cast<const uint4*>(h + (m0 + (idx >> 4)) * CH + (idx & 15) * 8)
+                              : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  auto stage = [&](int i) {                  // the fetched rows (swz256: conflict-free row reads) + W[:, block i]
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      *reinterpret_cast<uint4*>(smem + swz256(idx >> 4, idx & 15)) = pre[j];
+    }
+    for (int j = threadIdx.x; j < K * CH; j += 256) ws[j] = W[(j >> 7) * ldw + i * CH + (j & (CH - 1))];
+  };
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int i = 0; i < nb; ++i) {
+    if (i + 1 < nb) fetch(i + 1);
+    if (row < n) {
+#pragma unroll 4
+      for (int c = 0; c < 16; ++c) {
+        float v[8];
+        unpack8(*reinterpret_cast<const uint4*>(smem + swz256(row, c)), v);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float* wr = ws + k * CH + c * 8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[k] = fmaf(v[e], wr[e], acc[k]);
+        }
+      }
+    }
+    if (i + 1 < nb) {
+      __syncthreads();                       // every thread is done with block i's image
+      stage(i + 1);
+      __syncthreads();
+    }
+  }
+  if (row >= n) return;
+  if (gterm != nullptr) {
+    const float* gt = gterm + ((m0 + row) / L) * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] += gt[k];
+  }
+  float* o = out + (m0 + row) * K;
+#pragma unroll
+  for (int k = 0; k < K; ++k) o[k] = acc[k];
+}
+
+template <int K>
+int token_head_multi_fwd_launch(const MultiSrc& src, int nb, const float* W, const float* b, const float* gterm,
+                                float* out, long M, int L, hipStream_t st) {
+  static bool attr = false;                  // 64 KiB dynamic + the static weight slice exceed the default
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)token_head_multi_fwd_kernel<K>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 256);
+    attr = true;
+  }
+  hipLaunchKernelGGL(token_head_multi_fwd_kernel<K>, dim3((unsigned)((M + 255) / 256)), dim3(256), 256 * 256, st,
+                     src, nb, W, b, gterm, out, M, L);
+  return pbx_launch_status();
+}
+
+//   dW[k][i * 128 + c] = sum_m g[m][k] h_i[m][c]
+// One row of the concatenated features is nb * 16 chunks of 8 channels: thread = (row lane rl, block i,
+// chunk cc) with RL = 256 / (nb * 16) row lanes (threads past RL * nb * 16 idle), so a g row is fetched once
+// per workgroup for all nb blocks and each thread keeps the [KT][8] partial of its (i, cc) in registers over
+// the workgroup's rows (4 rows in flight per thread).  The row lanes are then summed in order through LDS and
+// the workgroup writes partial row blockIdx.x of the [P][K][nb * 128] slab (fixed order, no atomics).
+template <int KT>
+__global__ void __launch_bounds__(256) token_head_multi_wgrad_kernel(const MultiSrc src, const int nb,
+                                                                     const float* __restrict__ g,
+                                                                     float* __restrict__ slab, long M, int K) {
+  __shared__ __attribute__((aligned(16))) float red[256 * 8];
+  const int tid = threadIdx.x;
+  const int tpr = nb * 16, RL = 256 / tpr;
+  const int rl = tid / tpr, rem = tid - rl * tpr;
+  const int i = rem >> 4, cc = rem & 15;
+  const bool active = rl < RL;
+  constexpr int U = KT <= 8 ? 4 : 2;         // rows in flight per thread (KT = 16 holds 128 accumulators)
+  float acc[KT][8];
+#pragma unroll
+  for (int k = 0; k < KT; ++k)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[k][e] = 0.f;
+  if (active) {
+    const bf16_t* __restrict__ h = src.p[i] + cc * 8;
+    const long S = (long)gridDim.x * RL;
+    long row = (long)blockIdx.x * RL + rl;
+    for (; row + (U - 1) * S < M; row += U * S) {
+      uint4 q[U];
+      float gv[U][KT];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        q[u] = *reinterpret_cast<const uint4*>(h + (row + u * S) * CH);
+#pragma unroll
+        for (int k = 0; k < KT; ++k) gv[u][k] = k < K ? g[(row + u * S) * K + k] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        float hv[8];
+        unpack8(q[u], hv);
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[k][e] = fmaf(gv[u][k], hv[e], acc[k][e]);
+      }
+    }
+    for (; row < M; row += S) {
+      float hv[8];
+      unpack8(*reinterpret_cast<const uint4*>(h + row * CH), hv);
+#pragma unroll
+      for (int k = 0; k < KT; ++k) {
+        const float gk = k < K ? g[row * K + k] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[k][e] = fmaf(gk, hv[e], acc[k][e]);
+      }
+    }
+  }
+  float* dst = slab + (size_t)blockIdx.x * K * nb * CH + rem * 8;
+#pragma unroll
+  for (int k = 0; k < KT; ++k) {
+    if (k < K) {                             // uniform: the barriers below are reached by every thread
+      __syncthreads();                       // the previous class's partials have been summed
+      if (active) {
+        *reinterpret_cast<float4*>(red + tid * 8) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+        *reinterpret_cast<float4*>(red + tid * 8 + 4) = make_float4(acc[k][4], acc[k][5], acc[k][6], acc[k][7]);
+      }
+      __syncthreads();
+      if (tid < tpr) {
+        float s[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = red[tid * 8 + e];
+        for (int r = 1; r < RL; ++r)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s[e] += red[(r * tpr + tid) * 8 + e];
+        float* d = dst + (size_t)k * nb * CH;
+        *reinterpret_cast<float4*>(d) = make_float4(s[0], s[1], s[2], s[3]);
+        *reinterpret_cast<float4*>(d + 4) = make_float4(s[4], s[5], s[6], s[7]);
+      }
+    }
+  }
+}
+
+bool multi_src(const void* const* srcs, int nb, MultiSrc& ms) {
+  if (srcs == nullptr || nb < 1 || nb > MAXSRC) return false;
+  for (int i = 0; i < MAXSRC; ++i) {
+    ms.p[i] = (const bf16_t*)srcs[i < nb ? i : 0];
+    if ((reinterpret_cast<uintptr_t>(ms.p[i]) & 15) != 0 || ms.p[i] == nullptr) return false;   // 16-B row loads
+  }
+  return true;
+}
 }  // namespace
+
+// out [M][K] fp32 = b + sum_i h_i [M][128] bf16 . W[:, i*128:(i+1)*128]^T (W: [K][nb*128] fp32) + gterm[m / L]
+// srcs: HOST array of the nb (<= 8) device addresses; gterm ([ceil(M / L)][K] fp32) may be null; K <= 16
+PBX_EXPORT int pbx_token_head_multi_fwd(const void* const* srcs, int nb, const float* W, const float* b,
+                                        const float* gterm, float* out, long M, int K, int L, hipStream_t st) {
+  MultiSrc ms;
+  if (M < 1 || L < 1 || !multi_src(srcs, nb, ms)) return (int)hipErrorInvalidValue;
+  switch (K) {
+    case 1: return token_head_multi_fwd_launch<1>(ms, nb, W, b, gterm, out, M, L, st);
+    case 2: return token_head_multi_fwd_launch<2>(ms, nb, W, b, gterm, out, M, L, st);
+    case 3: return token_head_multi_fwd_launch<3>(ms, nb, W, b, gterm, out, M, L, st);
+    case 4: return token_head_multi_fwd_launch<4>(ms, nb, W, b, gterm, out, M, L, st);
+    case 5: return token_head_multi_fwd_launch<5>(ms, nb, W, b, gterm, out, M, L, st);
+    case 6: return token_head_multi_fwd_launch<6>(ms, nb, W, b, gterm, out, M, L, st);
+    case 7: return token_head_multi_fwd_launch<7>(ms, nb, W, b, gterm, out, M, L, st);
+    case 8: return token_head_multi_fwd_launch<8>(ms, nb, W, b, gterm, out, M, L, st);
+    case 9: return token_head_multi_fwd_launch<9>(ms, nb, W, b, gterm, out, M, L, st);
+    case 10: return token_head_multi_fwd_launch<10>(ms, nb, W, b, gterm, out, M, L, st);
+    case 11: return token_head_multi_fwd_launch<11>(ms, nb, W, b, gterm, out, M, L, st);
+    case 12: return token_head_multi_fwd_launch<12>(ms, nb, W, b, gterm, out, M, L, st);
+    case 13: return token_head_multi_fwd_launch<13>(ms, nb, W, b, gterm, out, M, L, st);
+    case 14: return token_head_multi_fwd_launch<14>(ms, nb, W, b, gterm, out, M, L, st);
+    case 15: return token_head_multi_fwd_launch<15>(ms, nb, W, b, gterm, out, M, L, st);
+    case 16: return token_head_multi_fwd_launch<16>(ms, nb, W, b, gterm, out, M, L, st);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+// slab: [P][K][nb*128] fp32 partials (P = number of workgroups, chosen by the caller); srcs as above; K <= 16
+PBX_EXPORT int pbx_token_head_multi_wgrad(const void* const* srcs, int nb, const float* g, float* slab, long M,
+                                          int K, int P, hipStream_t st) {
+  MultiSrc ms;
+  if (M < 1 || K < 1 || K > 16 || P < 1 || !multi_src(srcs, nb, ms)) return (int)hipErrorInvalidValue;
+  if (K <= 8)
+    hipLaunchKernelGGL(token_head_multi_wgrad_kernel<8>, dim3(P), dim3(256), 0, st, ms, nb, g, slab, M, K);
+  else
+    hipLaunchKernelGGL(token_head_multi_wgrad_kernel<16>, dim3(P), dim3(256), 0, st, ms, nb, g, slab, M, K);
+  return pbx_launch_status();
+}
 
 // out [M][K] fp32 = h [M][128] bf16 . W^T ([K][128] fp32) + b (K <= 16)
 PBX_EXPORT int pbx_token_head_fwd(const void* h, const float* W, const float* b, float* out, long M, int K,

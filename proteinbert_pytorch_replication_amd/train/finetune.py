@@ -74,7 +74,10 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
 
 
 def test_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, metrics: Dict[str, Callable],
-              device=None, distributed: bool = False) -> Tuple[float, Dict[str, float]]:
+              device=None, distributed: bool = False, collect: Optional[list] = None
+              ) -> Tuple[float, Dict[str, float]]:
+    """``collect``: a list that receives every batch's ``(outputs, y)`` (for metrics that are not batch means,
+    e.g. :func:`spearman` over the whole test set)."""
     device = torch.device(device or _default_device())
     model.eval()
     loss_sum = torch.zeros((), dtype=torch.float32, device=device)
@@ -88,6 +91,8 @@ def test_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, metr
             preds = torch.softmax(logits.float(), dim=1)
             for k, m in metrics.items():
                 met_sum[k] += _metric_value(m(preds, y)).to(device)
+            if collect is not None:
+                collect.append((logits.float(), y))
             n += 1
     return _finish(loss_sum, met_sum, n, distributed)
 
@@ -110,12 +115,63 @@ def token_accuracy(ignore_index: int = -100) -> Callable:
     return _acc
 
 
+def sequence_accuracy() -> Callable:
+    """Accuracy of a per-protein classifier; ``preds`` ``[B, K]`` probabilities, ``y`` ``[B]``."""
+    def _acc(preds: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return (preds.argmax(1) == y).float().mean()
+    return _acc
+
+
+def regression_loss() -> Callable:
+    """MSE between the ``[B, 1]`` output of an ``n_classes=1`` head and the float targets ``[B]``."""
+    def _mse(out: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return F.mse_loss(out.float().reshape(-1), y.float().reshape(-1))
+    return _mse
+
+
+def _average_ranks(v: torch.Tensor) -> torch.Tensor:
+    """1-based ranks of a 1-D tensor, tied values sharing the mean of the ranks they span (fp64)."""
+    v = v.reshape(-1)
+    order = torch.argsort(v, stable=True)
+    sv = v[order]
+    n = v.numel()
+    first = torch.ones(n, dtype=torch.bool, device=v.device)
+    first[1:] = sv[1:] != sv[:-1]
+    grp = torch.cumsum(first.long(), 0) - 1                       # tie group of every sorted element
+    pos = torch.arange(1, n + 1, dtype=torch.float64, device=v.device)
+    ng = int(grp[-1].item()) + 1 if n else 0
+    sums = torch.zeros(ng, dtype=torch.float64, device=v.device).index_add_(0, grp, pos)
+    cnt = torch.zeros(ng, dtype=torch.float64, device=v.device).index_add_(0, grp, torch.ones_like(pos))
+    ranks = torch.empty(n, dtype=torch.float64, device=v.device)
+    ranks[order] = (sums / cnt)[grp]
+    return ranks
+
+
+def spearman(pred: torch.Tensor, y: torch.Tensor) -> float:
+    """Spearman rank correlation of two equally long value sets: the Pearson correlation of their ranks, ties
+    given average ranks.  0.0 when either side is constant (the correlation is undefined there)."""
+    p, t = pred.detach().reshape(-1).double(), y.detach().reshape(-1).double()
+    if p.numel() != t.numel():
+        raise ValueError(f"spearman: {p.numel()} predictions for {t.numel()} targets")
+    if p.numel() < 2:
+        return 0.0
+    rp, rt = _average_ranks(p), _average_ranks(t)
+    rp, rt = rp - rp.mean(), rt - rt.mean()
+    den = torch.sqrt((rp * rp).sum() * (rt * rt).sum())
+    return float((rp * rt).sum() / den) if den > 0 else 0.0
+
+
 def finetune(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Optimizer, epochs: int = 1,
              test_dataloader=None, loss_fn: Optional[torch.nn.Module] = None, metrics: Optional[Dict] = None,
              gradient_clipping: bool = True, gradient_clipping_thresh: float = 1.0, device=None,
-             ddp=None, log: Optional[Callable[[str], None]] = None) -> Dict[str, Any]:
+             ddp=None, log: Optional[Callable[[str], None]] = None,
+             epoch_metrics: Optional[Dict[str, Callable]] = None) -> Dict[str, Any]:
     """Epoch loop around :func:`train_step` / :func:`test_step` (the shape of the reference's
-    commented ``train()``, ``utils.py:348-460``)."""
+    commented ``train()``, ``utils.py:348-460``).
+
+    ``epoch_metrics``: ``name -> fn(outputs, y)`` evaluated once per epoch on the model's raw outputs over the
+    whole test set (this rank's share of it), e.g. ``{"spearman": spearman}``: such a statistic is not a mean
+    of per-batch values.  Reported in ``results["test_metrics"]`` beside the batch-mean metrics."""
     loss_fn = loss_fn or torch.nn.CrossEntropyLoss(ignore_index=-100)
     metrics = metrics if metrics is not None else {"accuracy": token_accuracy()}
     results: Dict[str, Any] = {"train_loss": [], "test_loss": [], "train_metrics": [], "test_metrics": []}
@@ -127,7 +183,12 @@ def finetune(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
         results["train_loss"].append(tl)
         results["train_metrics"].append(tm)
         if test_dataloader is not None:
-            vl, vm = test_step(model, test_dataloader, loss_fn, metrics, device, ddp is not None)
+            seen: Optional[list] = [] if epoch_metrics else None
+            vl, vm = test_step(model, test_dataloader, loss_fn, metrics, device, ddp is not None, collect=seen)
+            if seen:
+                out_all, y_all = torch.cat([o for o, _ in seen]), torch.cat([t for _, t in seen])
+                for k, m in epoch_metrics.items():
+                    vm[k] = float(m(out_all, y_all))
             results["test_loss"].append(vl)
             results["test_metrics"].append(vm)
         if log is not None and pdist.is_main():
