@@ -92,21 +92,9 @@ __global__ void __launch_bounds__(256, 2) conv_dgrad4_kernel(
   float csum[8];
   float mean1 = 0.f, rstd1 = 0.f, m1 = 0.f, m2 = 0.f;
   if constexpr (FIN) {
-    // per-sample LN1 constants, computed by every wave (no barrier)
-    wave_ln_stats(fa.st1 + (size_t)b * fa.T1 * 2, fa.T1, fa.BM1, L, CH, fa.eps, mean1, rstd1);
-    wave_bwd_consts(fa.sums1 + (size_t)b * fa.TS1 * 2, fa.TS1, 1.0f / (float)(L * CH), m1, m2);
 #pragma unroll
     for (int e = 0; e < 8; ++e) csum[e] = 0.f;
   }
-  // dS1 chunk operands of position pos (clamped to a valid row; masked by the caller)
-  auto fin_load = [&](int pos, int c16, uint4& qd, uint4& qs, float4& ga, float4& gb) {
-    const int p = min(max(pos, 0), L - 1);
-    const size_t off = sbase + (size_t)p * CH + c16 * 8;
-    qd = *reinterpret_cast<const uint4*>(fa.dh1 + off);
-    qs = *reinterpret_cast<const uint4*>(fa.s1 + off);
-    ga = *reinterpret_cast<const float4*>(fa.g1 + (size_t)p * CH + c16 * 8);
-    gb = *reinterpret_cast<const float4*>(fa.g1 + (size_t)p * CH + c16 * 8 + 4);
-  };
   auto fin_ds1 = [&](bool ok, const uint4& qd, const uint4& qs, const float4& ga, const float4& gb) {
     float dv[8], sv[8], o[8];
     unpack8(qd, dv);
@@ -127,68 +115,139 @@ __global__ void __launch_bounds__(256, 2) conv_dgrad4_kernel(
   if constexpr (FIN) {
     // wide tile first: dS1 of each of its rows from dh1 / s1 / g1 -> dpre_w into aw; the rows the narrow
     // tile covers also park their dS1 in `an` (the narrow tile's own slot), so dh1 / s1 / g1 are read once
-    const int nchw = (BM + 2 * halo_w) * 16;
+    //
+    // Every global access of the staging is a branch-free buffer access on a per-sample descriptor: loads
+    // read a clamped, always-valid row and are masked at use, stores of masked lanes get an offset past
+    // num_records and are dropped by the range check (an `if` around either becomes an exec-mask branch
+    // with a vmcnt(0) at its join).  The wide pass runs as trips of WK chunks per thread, the next trip's
+    // loads issued before this trip is converted (two operand sets, the loop unrolled by two so that no
+    // register copy waits for the prefetch); the narrow pass's GELU' loads and the LN1 partials are in
+    // flight from the start.  The empty asm statements keep the buffer accesses in the order written.
+    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+    constexpr int VO_DROP = 0x7ffffff0;
+    constexpr int WK = 2;                            // chunks per thread and trip of the wide pass
+    constexpr int NSP = 8;                           // LN1 backward partials per lane loaded up front
+    auto issue_fence = [] { asm volatile("" ::: "memory"); };
+    auto rsrc_of = [](const void* p, int bytes) {
+      return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
+    };
+    auto ldq = [](const __amdgpu_buffer_rsrc_t& rs, int vo) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0);
+      return make_uint4(v[0], v[1], v[2], v[3]);
+    };
+    auto ldf = [](const __amdgpu_buffer_rsrc_t& rs, int vo) {
+      return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
+    };
+    auto stq = [](const __amdgpu_buffer_rsrc_t& rs, int vo, const uint4& q) {
+      __builtin_amdgcn_raw_buffer_store_b128((u32x4){q.x, q.y, q.z, q.w}, rs, vo, 0, 0);
+    };
+    const int sbytes = L * CH * 2;                   // one sample's rows of a bf16 tensor
+    const __amdgpu_buffer_rsrc_t rdh = rsrc_of(fa.dh1 + sbase, sbytes), rs1 = rsrc_of(fa.s1 + sbase, sbytes);
+    const __amdgpu_buffer_rsrc_t rgw = rsrc_of(gdw + sbase, sbytes), rgn = rsrc_of(gdn + sbase, sbytes);
+    const __amdgpu_buffer_rsrc_t rg1 = rsrc_of(fa.g1, 2 * sbytes);
+    const __amdgpu_buffer_rsrc_t rpw = rsrc_of(dpre_w + sbase, sbytes), rpn = rsrc_of(dpre_n + sbase, sbytes);
+    const int nchw = (BM + 2 * halo_w) * 16;         // a multiple of 64: a wave's chunks are all in or all out
     const int joff = halo_w - halo_n;                // wide row of narrow row 0
-    for (int base = tid; base < nchw; base += 4 * 256) {
-      uint4 qd[4], qs[4], pq[4];
-      float4 ga[4], gb[4];
+    const int ch = tid & 15;
+    struct WideOps {
+      uint4 qd[WK], qs[WK], pq[WK];
+      float4 ga[WK], gb[WK];
+    };
+    auto wide_load = [&](int trip, WideOps& w) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int idx = base + i * 256;
-        const int pos = pos0 - halo_w + (idx >> 4);
-        fin_load(pos, idx & 15, qd[i], qs[i], ga[i], gb[i]);
-        pq[i] = *reinterpret_cast<const uint4*>(gdw + sbase + (size_t)min(max(pos, 0), L - 1) * CH + (idx & 15) * 8);
+      for (int i = 0; i < WK; ++i) {
+        const int idx = (trip * WK + i) * 256 + tid;
+        const int p = min(max(pos0 - halo_w + (idx >> 4), 0), L - 1);
+        const int vo = (p * CH + ch * 8) * 2;
+        w.qd[i] = ldq(rdh, vo);
+        w.qs[i] = ldq(rs1, vo);
+        w.ga[i] = ldf(rg1, 2 * vo);
+        w.gb[i] = ldf(rg1, 2 * vo + 16);
+        w.pq[i] = ldq(rgw, vo);
       }
+      issue_fence();
+    };
+    // one trip: WK buffer stores whatever the lanes hold (the compiler's wait counts rely on it)
+    auto wide_conv = [&](int trip, const WideOps& w) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int idx = base + i * 256;
-        if (idx >= nchw) break;
-        const int j = idx >> 4, ch = idx & 15;
+      for (int i = 0; i < WK; ++i) {
+        const int idx = (trip * WK + i) * 256 + tid;
+        const int j = idx >> 4;
         const int pos = pos0 - halo_w + j;
         const bool ok = pos >= 0 && pos < L;
-        const uint4 dq = fin_ds1(ok, qd[i], qs[i], ga[i], gb[i]);
-        const uint4 v = ok ? dpre_of(dq, pq[i]) : make_uint4(0u, 0u, 0u, 0u);
-        if (ok && j >= halo_w && j < halo_w + BM)
-          *reinterpret_cast<uint4*>(dpre_w + sbase + (size_t)pos * CH + ch * 8) = v;
-        *reinterpret_cast<uint4*>(aw + swz256(j, ch)) = v;
-        if (j >= joff && j < joff + RN) *reinterpret_cast<uint4*>(an + swz256(j - joff, ch)) = dq;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if ((trip * WK + i) * 256 + cq * 64 < nchw) {          // wave-uniform
+          const uint4 dq = fin_ds1(ok, w.qd[i], w.qs[i], w.ga[i], w.gb[i]);
+          v = ok ? dpre_of(dq, w.pq[i]) : make_uint4(0u, 0u, 0u, 0u);
+          *reinterpret_cast<uint4*>(aw + swz256(j, ch)) = v;
+          if (j >= joff && j < joff + RN) *reinterpret_cast<uint4*>(an + swz256(j - joff, ch)) = dq;
+        }
+        stq(rpw, ok && j >= halo_w && j < halo_w + BM ? (pos * CH + ch * 8) * 2 : VO_DROP, v);
       }
+      issue_fence();
+    };
+    WideOps wa, wb;
+    wide_load(0, wa);
+    // this lane's LN1 partials and the narrow pass's GELU' chunks, all in flight before the first wait
+    const float* st1b = fa.st1 + (size_t)b * fa.T1 * 2;
+    const float* sums1b = fa.sums1 + (size_t)b * fa.TS1 * 2;
+    const float2 pm = ln_part(st1b, lane, fa.T1);
+    float2 ps[NSP];
+#pragma unroll
+    for (int k = 0; k < NSP; ++k) ps[k] = ln_part(sums1b, lane + 64 * k, fa.TS1);
+    issue_fence();
+    uint4 pqn[9];
+#pragma unroll
+    for (int m = 0; m < 9; ++m) {
+      const int p = min(max(pos0 - halo_n + ((tid + 256 * m) >> 4), 0), L - 1);
+      pqn[m] = ldq(rgn, (p * CH + ch * 8) * 2);
     }
+    issue_fence();
+    // as many dropped stores as a trip issues after its prefetch: the first trip's wait then has the
+    // count of the steady state and leaves the stores of the trip before outstanding
+#pragma unroll
+    for (int i = 0; i < WK; ++i) {
+      __builtin_amdgcn_raw_buffer_store_b32(0u, rpw, VO_DROP - 16 * i, 0, 0);
+      issue_fence();
+    }
+    // per-sample LN1 constants, computed by every wave (no barrier)
+    wave_ln_stats_from(pm, st1b, fa.T1, fa.BM1, L, CH, fa.eps, mean1, rstd1);
+    wave_bwd_consts_from<NSP>(ps, sums1b, fa.TS1, 1.0f / (float)(L * CH), m1, m2);
+    const int ntrip = (nchw + WK * 256 - 1) / (WK * 256);
+    int trip = 0;
+    for (; trip + 2 < ntrip; trip += 2) {
+      wide_load(trip + 1, wb);
+      wide_conv(trip, wa);
+      wide_load(trip + 2, wa);
+      wide_conv(trip + 1, wb);
+    }
+    // the last pair on its own: nothing is fetched past it (a load skipped inside the loop would lower
+    // the loop's wait counts to those of the path without it)
+    wide_load(trip + 1, wb);
+    wide_conv(trip, wa);
+    wide_conv(trip + 1, wb);
     __syncthreads();
     // narrow tile (RN = BM + 8 rows x 16 chunks): fully unrolled so the central rows' dS1 stay in
     // registers; each thread converts its own chunks of `an` in place (dS1 -> dpre_n)
-    const int nch = RN * 16;
+    const int nch = RN * 16;                         // a multiple of 64 too
 #pragma unroll
-    for (int mb = 0; mb < 9; mb += 3) {
-      uint4 pq[3];
+    for (int m = 0; m < 9; ++m) {
+      const int idx = tid + 256 * m;
+      const int j = idx >> 4;
+      const int pos = pos0 - halo_n + j;
+      const bool live = 256 * m + cq * 64 < nch;     // wave-uniform
+      const bool ok = live && pos >= 0 && pos < L;
+      const bool mid = ok && j >= halo_n && j < halo_n + BM;
+      uint4 dq = make_uint4(0u, 0u, 0u, 0u);
+      if (live) dq = *reinterpret_cast<const uint4*>(an + swz256(j, ch));
+      keep[m] = dq;
+      float t[8];
+      unpack8(dq, t);
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int idx = tid + 256 * (mb + i);
-        const int pos = pos0 - halo_n + (idx >> 4);
-        pq[i] = *reinterpret_cast<const uint4*>(gdn + sbase + (size_t)min(max(pos, 0), L - 1) * CH + (idx & 15) * 8);
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int m = mb + i;
-        const int idx = tid + 256 * m;
-        const int j = idx >> 4, ch = idx & 15;
-        const int pos = pos0 - halo_n + j;
-        const bool ok = idx < nch && pos >= 0 && pos < L;
-        const uint4 dq = idx < nch ? *reinterpret_cast<const uint4*>(an + swz256(j, ch)) : make_uint4(0u, 0u, 0u, 0u);
-        keep[m] = dq;
-        if (ok && j >= halo_n && j < halo_n + BM) {
-          float t[8];
-          unpack8(dq, t);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) csum[e] += t[e];
-        }
-        if (idx < nch) {
-          const uint4 v = ok ? dpre_of(dq, pq[i]) : make_uint4(0u, 0u, 0u, 0u);
-          if (ok && j >= halo_n && j < halo_n + BM)
-            *reinterpret_cast<uint4*>(dpre_n + sbase + (size_t)pos * CH + ch * 8) = v;
-          *reinterpret_cast<uint4*>(an + swz256(j, ch)) = v;
-        }
-      }
+      for (int e = 0; e < 8; ++e) csum[e] += mid ? t[e] : 0.f;
+      const uint4 v = ok ? dpre_of(dq, pqn[m]) : make_uint4(0u, 0u, 0u, 0u);
+      stq(rpn, mid ? (pos * CH + ch * 8) * 2 : VO_DROP, v);
+      if (live) *reinterpret_cast<uint4*>(an + swz256(j, ch)) = v;
     }
   }
   // stage dpre = dS1 * GELU'(pre) of both convs with their halos; central rows also go to global

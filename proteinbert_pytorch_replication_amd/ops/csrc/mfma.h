@@ -209,6 +209,58 @@ __device__ __forceinline__ void wave_bwd_consts(const float* __restrict__ part, 
   m2 = wave_reduce_sum(c) * inv_n;
 }
 
+// wave_ln_stats / wave_bwd_consts with the loads taken out: the caller issues this lane's first partials
+// (tile `lane` of `part`; NP backward partials lane, lane + 64, ... -- all at clamped, always-valid
+// addresses) among its other loads, and the reduce runs when they have landed.  Partials past the prefetched
+// ones are walked as in the functions above.  Same merge order and arithmetic, so the same bits.
+__device__ __forceinline__ float2 ln_part(const float* __restrict__ part, int t, int T) {
+  return *reinterpret_cast<const float2*>(part + 2 * min(t, T - 1));
+}
+// the same, kept where it is written: the compiler otherwise sinks the load into the branch that uses it
+__device__ __forceinline__ float2 ln_part_here(const float* __restrict__ part, int t, int T) {
+  float2 v = ln_part(part, t, T);
+  asm volatile("" : "+v"(v.x), "+v"(v.y));
+  return v;
+}
+__device__ __forceinline__ void wave_ln_stats_from(float2 pm, const float* __restrict__ part, int T, int BM, int L,
+                                                   int C, float eps, float& mean, float& rstd) {
+  const int lane = threadIdx.x & 63;
+  float n = 0.f, m = 0.f, M2 = 0.f;
+  if (lane < T) chan_merge(n, m, M2, (float)(min(BM, L - lane * BM) * C), pm.x, pm.y);
+  for (int t0 = 64; t0 < T; t0 += 64) {          // wave-uniform trips, clamped loads
+    const int t = t0 + lane;
+    const float2 pt = ln_part_here(part, t, T);
+    if (t < T) chan_merge(n, m, M2, (float)(min(BM, L - t * BM) * C), pt.x, pt.y);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float nb = __shfl_xor(n, o, 64), mb = __shfl_xor(m, o, 64), M2b = __shfl_xor(M2, o, 64);
+    chan_merge(n, m, M2, nb, mb, M2b);
+  }
+  mean = m;
+  rstd = rsqrtf(M2 / n + eps);
+}
+template <int NP>
+__device__ __forceinline__ void wave_bwd_consts_from(const float2* ps, const float* __restrict__ part, int T,
+                                                     float inv_n, float& m1, float& m2) {
+  const int lane = threadIdx.x & 63;
+  float a = 0.f, c = 0.f;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const bool in = lane + 64 * k < T;
+    a = in ? a + ps[k].x : a;
+    c = in ? c + ps[k].y : c;
+  }
+  for (int t0 = 64 * NP; t0 < T; t0 += 64) {
+    const float2 pt = ln_part_here(part, t0 + lane, T);
+    const bool in = t0 + lane < T;
+    a = in ? a + pt.x : a;
+    c = in ? c + pt.y : c;
+  }
+  m1 = wave_reduce_sum(a) * inv_n;
+  m2 = wave_reduce_sum(c) * inv_n;
+}
+
 // (count, mean, M2) of one wave's values: each lane contributes cnt values with sum s and sum of
 // squared deviations from its own mean q; merged across the wave.  Returned on every lane.
 __device__ __forceinline__ void wave_chan(float& n, float& m, float& M2) {

@@ -55,8 +55,10 @@ CONV_FWD5 = os.environ.get("PBX_CONV_FWD", "5") == "5"
 def conv_dgrad_fin(dh1, s1, st1, T1, BM1, sums1, TS1, g1, gdn, gdw, wtn, wtw, dx, dpn, dpw, dgb, B, L, KS, dil,
                    stream):
     """Conv data gradient with the LayerNorm-1 backward finalize fused in (whole sequences, conv_dgrad4<FIN>):
-    dx, both convs' dpre (for the weight gradient) and dgb += the column sums of dS1.  (A persistent form with
-    the staging pipelined into the K loop measured no better in the step: profiles/r6/conv_dgrad5_attempts.txt.)"""
+    dx, both convs' dpre (for the weight gradient) and dgb += the column sums of dS1.  Its staging pass keeps its
+    loads in flight (the next trip of the wide tile prefetched, branch-free buffer accesses, counted waits:
+    profiles/r16/dgrad_waits.txt).  (A persistent form with the staging pipelined into the K loop measured no
+    better in the step: profiles/r6/conv_dgrad5_attempts.txt.)"""
     _lib.call("pbx_conv_dgrad4f", dh1.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, BM1, sums1.data_ptr(),
               TS1, g1.data_ptr(), gdn.data_ptr(), gdw.data_ptr(), wtn.data_ptr(), wtw.data_ptr(),
               dx.data_ptr(), dpn.data_ptr(), dpw.data_ptr(), dgb.data_ptr(), B, L, KS, dil, LN_EPS, stream)

@@ -4,9 +4,15 @@ at the bench shape through their exported launchers (whole sequences: no context
 whatever library PBX_HIP_LIB names (a variant built by tools/ubench/build_flags.sh).
 
     python tools/ubench/convbench.py [--B 1024 --L 512]
+    python tools/ubench/convbench.py --B 2048 --fin-ab parent=tools/ubench/abl/libpbx_parent.so new=<...>/libpbx_hip.so
+
+--fin-ab: the FIN form of the data gradient for several builds of the library in ONE process, rounds interleaved
+(--rounds x --calls), with the step's LN1 partial counts (T1 = L / 128, TS1 = L / 2); median / min / max us per call.
 """
 import argparse
+import ctypes
 import os
+import statistics
 import sys
 
 import torch
@@ -19,6 +25,9 @@ ap.add_argument("--B", type=int, default=1024)
 ap.add_argument("--L", type=int, default=512)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--tag", default="")
+ap.add_argument("--fin-ab", nargs="*", default=[], metavar="name=path")
+ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--calls", type=int, default=10)
 a = ap.parse_args()
 B, L, C, KS, dil = a.B, a.L, 128, 9, 5
 dev = torch.device("cuda")
@@ -75,6 +84,46 @@ fin_args = lambda: [dh1.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, 128, sums
                     dpw.data_ptr(), dgb.data_ptr()]
 us = timeit(lambda: _lib.call("pbx_conv_dgrad4f", *fin_args(), B, L, KS, dil, 1e-5, st))
 print(f"[{a.tag}] conv_dgrad4<FIN> {us:8.1f} us  {flops / us / 1e6:7.1f} TFLOP/s", flush=True)
+if a.fin_ab:
+    def load(path):
+        lib = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        lib.pbx_conv_dgrad4f.argtypes, lib.pbx_conv_dgrad4f.restype = _lib.launchers()["pbx_conv_dgrad4f"], ctypes.c_int
+        return lib
+    libs = [(s.split("=", 1)[0], load(s.split("=", 1)[1])) for s in a.fin_ab]
+    TS1 = (L + 1) // 2
+    sums_ab = torch.randn(B, TS1, 2, device=dev)
+    outs = {n: [torch.empty_like(x) for _ in range(3)] for n, _ in libs}
+
+    def fin(n, lib):
+        o = outs[n]
+        return lib.pbx_conv_dgrad4f(dh1.data_ptr(), s1.data_ptr(), st1.data_ptr(), T1, 128, sums_ab.data_ptr(), TS1,
+                                    g1.data_ptr(), pre_n.data_ptr(), pre_w.data_ptr(), ft.data_ptr(), ft.data_ptr(),
+                                    o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), dgb.data_ptr(), B, L, KS, dil,
+                                    1e-5, st)
+    for n, lib in libs:
+        assert fin(n, lib) == 0
+    torch.cuda.synchronize()
+    first = outs[libs[0][0]]
+    for n, _ in libs[1:]:
+        same = [torch.equal(p.view(torch.int16), q.view(torch.int16)) for p, q in zip(first, outs[n])]
+        print(f"{n} vs {libs[0][0]}: dx / dpre_n / dpre_w bitwise equal: {same}", flush=True)
+    times = {n: [] for n, _ in libs}
+    for _ in range(a.rounds):
+        for n, lib in libs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.calls):
+                rc = fin(n, lib)
+            e1.record()
+            e1.synchronize()
+            assert rc == 0, rc
+            times[n].append(e0.elapsed_time(e1) * 1e3 / a.calls)
+    print(f"conv_dgrad4<FIN> B={B} L={L} rounds={a.rounds} calls/round={a.calls} (us per call, launch gaps included)")
+    for n, _ in libs:
+        t = times[n]
+        print(f"  {n:10s} median {statistics.median(t):7.1f} min {min(t):7.1f} max {max(t):7.1f}   "
+              f"{flops / statistics.median(t) / 1e6:6.1f} TFLOP/s", flush=True)
+    sys.exit(0)
 slab = torch.empty(64 * 2 * KS * C * C, device=dev)
 bslab = torch.empty(64 * 2 * C, device=dev)
 dwn, dww = torch.zeros(C, C, KS, device=dev), torch.zeros(C, C, KS, device=dev)
