@@ -14,7 +14,9 @@ default): per-residue classes, CSV columns ``seq`` and ``labels`` (one class cha
 given by ``--classes``).  ``--task sequence``: per-protein classes, columns ``seq`` and ``label`` (an integer in
 ``0..n-1``, ``--n-classes n``), accuracy.  ``--task regression``: columns ``seq`` and ``label`` (a float), MSE
 loss and the test set's Spearman correlation per epoch.  ``--hidden all`` puts the head on every block's hidden
-state instead of the last block's (:mod:`..models.finetune`).
+state instead of the last block's (:mod:`..models.finetune`).  The head is saved as
+``proteinbert_finetuned_head.pt`` (``"head"`` in the printed JSON); ``--unfreeze`` also saves the encoder it
+trained as a model file (``"encoder"``), the pair ``cli predict --model ... --head NAME=...`` takes.
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ from ..config import RunConfig, apply_overrides, get_preset, load_yaml, PRESETS
 from ..data import SyntheticUniRefGO, CorruptionParams
 from ..models import (ProteinBERT, ProteinBERTForSequenceClassification, ProteinBERTForTokenClassification,
                       build_model)
+from ..models.finetune import build_finetune_model, load_finetuned_head  # noqa: F401  (their home; names kept here)
 from ..utils import determinism
 from ..parallel import dist as pdist
 
@@ -202,31 +205,6 @@ def _seq_csv(path: str, L: int, regression: bool, n_classes: int):
 FINETUNE_TASKS = ("residue", "sequence", "regression")
 
 
-def build_finetune_model(enc: ProteinBERT, meta: dict, freeze_encoder: bool = True):
-    """The head class a saved head file's ``meta`` describes (:func:`load_finetuned_head`)."""
-    if meta["task"] == "residue":
-        return ProteinBERTForTokenClassification(enc, n_classes=meta["n_classes"], freeze_encoder=freeze_encoder,
-                                                 use_global=meta["use_global"], hidden=meta["hidden"])
-    return ProteinBERTForSequenceClassification(enc, n_classes=meta["n_classes"], freeze_encoder=freeze_encoder,
-                                                hidden=meta["hidden"])
-
-
-def load_finetuned_head(path: str, enc: ProteinBERT, freeze_encoder: bool = True):
-    """Rebuild the fine-tuned model of a ``proteinbert_finetuned_head.pt`` around ``enc``.  The file's ``"meta"``
-    entry names the task and head form; a file without it is a ``hidden="last"`` per-residue head."""
-    state = dict(torch.load(path, map_location="cpu"))
-    meta = state.pop("meta", None)
-    if meta is None:
-        meta = {"task": "residue", "hidden": "last", "n_classes": state["head.weight"].shape[0], "classes": None,
-                "use_global": "global_head.weight" in state}
-    model = build_finetune_model(enc, meta, freeze_encoder)
-    missing, unexpected = model.load_state_dict(state, strict=False)
-    if unexpected or any(not k.startswith("encoder.") for k in missing):
-        raise ValueError(f"{path}: head does not fit meta {meta}: missing "
-                         f"{[k for k in missing if not k.startswith('encoder.')]}, unexpected {unexpected}")
-    return model, meta
-
-
 def finetune_main(argv: Optional[List[str]] = None) -> dict:
     ap = argparse.ArgumentParser(description="ProteinBERT fine-tuning: per-residue / per-protein task heads")
     _common(ap)
@@ -338,5 +316,11 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
             head["meta"] = meta
         torch.save(head, path)
         res["head"] = path
-        print(json.dumps({"train_loss": res["train_loss"], "test_metrics": res["test_metrics"], "head": path}))
+        summary = {"train_loss": res["train_loss"], "test_metrics": res["test_metrics"], "head": path}
+        if a.unfreeze:
+            # the head file holds no encoder entries: without the encoder it was trained with, the head could
+            # never be used (inference.Predictor(load_model(encoder), heads={...: head file}))
+            from ..train.checkpoint import save_final_model
+            res["encoder"] = summary["encoder"] = save_final_model(model.encoder, cfg.train.save_path)
+        print(json.dumps(summary))
     return res

@@ -17,7 +17,25 @@ token tensors), any subset of
 ``hidden_states``    ``hidden_global`` ``[N, blocks, G]`` / ``hidden_pooled``    fp32
                      ``[N, blocks, 128]``: ``global`` / ``pooled`` after every
                      block
+``task:NAME``        ``task_NAME_labels`` / ``task_NAME_label_probs``:           int32 / fp32
+                     ``[N, L]`` (residue head) or ``[N]`` (per-protein
+                     classifier); a regression head (``n_classes == 1``) gives
+                     ``task_NAME_values`` ``[N]`` (fp32) instead
+``task_probs:NAME``  ``task_NAME_probs``: ``[N, L, K]`` (residue head) or        fp32
+                     ``[N, n]`` (per-protein classifier); a regression head
+                     raises ``ValueError``
 ===================  ==========================================================  =======================
+
+``task:NAME`` / ``task_probs:NAME`` exist for the fine-tuned heads registered as ``Predictor(model,
+heads={NAME: head})`` (:mod:`.models.finetune`; a head instance around ``model``, or the path of a file written
+by ``cli finetune``); any other name raises ``unknown outputs``.  Only the head's own layers are used (``head``,
+``global_head``), on the batch's single encoder pass, whatever the number of heads.  A residue head's call is the
+lowest class of maximal probability; at the positions fine-tuning ignores (``<pad>``, ``<sos>``, ``<eos>``: token
+id below ``UNK_ID``, the ones ``cli finetune`` labels -100) the label is -1, the probability 0 and the
+probability row zero.  On the HIP backend a residue head is one launch of ``pbx_token_head_calls``
+(:func:`.ops.infer_heads.token_head_calls`) whose logits never leave the registers; its global term
+(``global_head`` of ``g``, or of the concatenated per-block ``g_i``) is a ``[B, K]`` torch op.  The per-protein
+heads are ``[B, n]``-sized torch ops on both backends: a few KB per batch, where a kernel would gain nothing.
 
 Only the requested heads run.  On the HIP backend (``model.resolved_backend(device) == "hip"``) the encoder is
 :func:`.ops.fused_model.fused_encode` and the heads are the fused kernels of :mod:`.ops.infer_heads`; on the
@@ -32,29 +50,67 @@ and a batch of one gives probabilities of exactly 1 everywhere.  That is the ref
 corrected here: :meth:`Predictor.predict` normalises over each of its batches of ``batch_size`` sequences (the
 last one may be smaller), on this process only.  Keep ``batch_size`` and the input order fixed to compare
 runs, or use a ``semantics="paper"`` model (softmax over the vocabulary), whose predictions are per sequence.
-Embeddings and GO predictions do not depend on the batch in either semantics.
+Embeddings and GO predictions do not depend on the batch in either semantics.  Neither do the ``task:`` /
+``task_probs:`` outputs: a task head's softmax runs over its classes, per residue or per protein, so they are
+per sequence whatever the model's semantics (the encoder itself never mixes sequences).
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Optional, Sequence, Union
+import os
+import re
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from .data.transforms import SimpleCharacterTokenizer, pad_to
 from .data.vocab import PAD_ID, create_amino_acid_vocab
+from .models.finetune import (ProteinBERTForSequenceClassification, ProteinBERTForTokenClassification,
+                              load_finetuned_head)
 
 OUTPUTS = ("global", "pooled", "residue", "go_probs", "go_topk", "residue_probs", "residue_tokens", "hidden_states")
 DEFAULT_OUTPUTS = ("global", "pooled", "go_topk")
 
 
-def _check_outputs(outputs: Iterable[str]) -> tuple:
+TASK_PREFIXES = ("task:", "task_probs:")
+_HEAD_NAME = re.compile(r"[A-Za-z][A-Za-z0-9_]*\Z")
+
+
+def _task_request(o) -> Optional[Tuple[str, str]]:
+    """``("task" | "task_probs", NAME)`` of a task output name, else None."""
+    if isinstance(o, str):
+        for p in TASK_PREFIXES:
+            if o.startswith(p) and _HEAD_NAME.match(o[len(p):]):
+                return p[:-1], o[len(p):]
+    return None
+
+
+def _check_outputs(outputs: Iterable[str], heads: Optional[dict] = None) -> tuple:
+    """The requested names as a tuple: the built-in ``OUTPUTS`` and ``task:NAME`` / ``task_probs:NAME`` of the
+    registered ``heads``; anything else is ``unknown outputs``."""
     if isinstance(outputs, str):
         outputs = (outputs,)
     outputs = tuple(outputs)
-    bad = [o for o in outputs if o not in OUTPUTS]
+    heads = heads or {}
+    reqs = [_task_request(o) for o in outputs]
+    bad = [o for o, r in zip(outputs, reqs) if o not in OUTPUTS and (r is None or r[1] not in heads)]
     if bad:
-        raise ValueError(f"unknown outputs {bad}: expected a subset of {OUTPUTS}")
+        tasks = tuple(p + n for n in heads for p in TASK_PREFIXES)
+        raise ValueError(f"unknown outputs {bad}: expected a subset of {OUTPUTS + tasks}")
+    for o, r in zip(outputs, reqs):
+        if o not in OUTPUTS and r[0] == "task_probs" and _is_regression(heads[r[1]]):
+            raise ValueError(f"{o}: {r[1]!r} is a regression head (n_classes == 1), it has values, not "
+                             f"probabilities: request task:{r[1]}")
     return outputs
+
+
+def _is_regression(head) -> bool:
+    return isinstance(head, ProteinBERTForSequenceClassification) and head.n_classes == 1
+
+
+def _calls_torch(p: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(labels int32, their probabilities)`` over the last axis of ``p``: the first maximal index."""
+    i = p.argmax(dim=-1)
+    return i.to(torch.int32), p.gather(-1, i.unsqueeze(-1)).squeeze(-1)
 
 
 def masked_mean_torch(h: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
@@ -74,15 +130,37 @@ def stable_topk_torch(p: torch.Tensor, k: int):
 class Predictor:
     """Inference on ``model`` (see the module docstring for the outputs and for how reference-semantics local
     predictions depend on the batch).  ``batch_size``: sequences per encoder pass of :meth:`predict`;
-    ``device``: where the model runs (default: where its parameters are)."""
+    ``device``: where the model runs (default: where its parameters are).  ``heads``: fine-tuned task heads by
+    name (``[A-Za-z][A-Za-z0-9_]*``), each a :class:`~.models.ProteinBERTForTokenClassification` or
+    :class:`~.models.ProteinBERTForSequenceClassification` whose ``.encoder`` is ``model``, or the path of a
+    head file of ``cli finetune``, which is loaded around ``model`` (``head_meta[name]`` then holds the file's
+    meta).  The head of an unfrozen fine-tune goes with its own encoder: ``Predictor(ft.encoder, heads={"ss":
+    ft})``."""
 
-    def __init__(self, model, batch_size: int = 256, device=None):
+    def __init__(self, model, batch_size: int = 256, device=None, heads: Optional[dict] = None):
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
         self.model = model
         self.batch_size = int(batch_size)
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         self.tokenizer = SimpleCharacterTokenizer(create_amino_acid_vocab(), add_sos_eos=True)
+        self.heads: Dict[str, torch.nn.Module] = {}
+        self.head_meta: Dict[str, Optional[dict]] = {}
+        for name, head in (heads or {}).items():
+            if not isinstance(name, str) or not _HEAD_NAME.match(name):
+                raise ValueError(f"head name {name!r}: expected [A-Za-z][A-Za-z0-9_]*")
+            meta = None
+            if isinstance(head, (str, os.PathLike)):
+                # freeze_encoder=False: building the head must not touch the model's requires_grad flags
+                head, meta = load_finetuned_head(os.fspath(head), model, freeze_encoder=False)
+            if not isinstance(head, (ProteinBERTForTokenClassification, ProteinBERTForSequenceClassification)):
+                raise TypeError(f"head {name!r}: expected a fine-tuning model or the path of a head file, got "
+                                f"{type(head).__name__}")
+            if head.encoder is not model:
+                raise ValueError(f"head {name!r} was built around another encoder: predict with "
+                                 f"Predictor(head.encoder, heads={{{name!r}: head}})")
+            self.heads[name] = head
+            self.head_meta[name] = meta
 
     # ------------------------------------------------------------------------
     def tokenize(self, sequences: Sequence[str], truncate: bool = False) -> torch.Tensor:
@@ -113,22 +191,71 @@ class Predictor:
                       outputs: Iterable[str] = DEFAULT_OUTPUTS, go_top_k: int = 10) -> Dict[str, torch.Tensor]:
         """One encoder pass over ``tokens [B, L]`` int64 (and ``annotations [B, A]``, zeros when None):
         the requested outputs as tensors on the model's device, without any host synchronisation."""
-        outputs = _check_outputs(outputs)
+        outputs = _check_outputs(outputs, self.heads)
         model = self.model
         A = model.config["num_annotations"]
         if ("go_topk" in outputs) and not 1 <= go_top_k <= A:
             raise ValueError(f"go_top_k={go_top_k}: expected 1 .. {A}")
         tokens = tokens.to(self.device, non_blocking=True)
         ann = self._annotations(annotations, tokens.shape[0], self.device)
-        was_training = model.training
+        # eval() for the model and the heads; every module's own flag is put back (a head holds the model as
+        # its .encoder, so head.train(mode) alone would overwrite the model's)
+        modes = [(m, m.training) for root in (model, *self.heads.values()) for m in root.modules()]
         model.eval()
+        for head in self.heads.values():
+            head.eval()
         try:
             with torch.no_grad():
                 if model.resolved_backend(self.device) == "hip":
                     return self._predict_hip(tokens, ann, outputs, go_top_k)
                 return self._predict_torch(tokens, ann, outputs, go_top_k)
         finally:
-            model.train(was_training)
+            for m, mode in modes:
+                m.training = mode
+
+    # ------------------------------------------------------------------------
+    def _task_requests(self, outputs) -> Dict[str, set]:
+        """Registered head name -> the kinds (``"task"``, ``"task_probs"``) requested of it."""
+        req: Dict[str, set] = {}
+        for o in outputs:
+            r = None if o in OUTPUTS else _task_request(o)
+            if r is not None:
+                req.setdefault(r[1], set()).add(r[0])
+        return req
+
+    def _needs_all(self, req) -> bool:
+        return any(self.heads[n].hidden == "all" for n in req)
+
+    def _task_outputs(self, out, req, tokens, h, g, hs_all, gs_all, hip: bool) -> None:
+        """The outputs of the requested task heads from this batch's encoder pass: ``h`` / ``g`` the final
+        states, ``hs_all`` / ``gs_all`` every block's (filled only when a ``hidden="all"`` head asked)."""
+        from .ops import finetune_head
+        from .ops import infer_heads as ih
+        for name, kinds in req.items():
+            head = self.heads[name]
+            every = head.hidden == "all"
+            gfeat = torch.cat([x.float() for x in gs_all], dim=-1) if every else g.float()
+            if isinstance(head, ProteinBERTForTokenClassification):
+                hs = list(hs_all) if every else [h]
+                gterm = head.global_head(gfeat) if head.global_head is not None else None       # [B, K]
+                fn = (ih.token_head_calls if hip and finetune_head.supported_multi(hs, head.n_classes)
+                      else ih.token_head_calls_torch)      # outside the kernel's range (K > 16, C != 128): torch
+                P, lab, pmax = fn(hs, head.head.weight, head.head.bias, gterm, tokens,
+                                  store_probs="task_probs" in kinds)
+                if "task" in kinds:
+                    out[f"task_{name}_labels"], out[f"task_{name}_label_probs"] = lab, pmax
+                if "task_probs" in kinds:
+                    out[f"task_{name}_probs"] = P
+                continue
+            z = head.head(gfeat).float()                                                        # [B, n]
+            if head.n_classes == 1:
+                out[f"task_{name}_values"] = z[:, 0]
+                continue
+            p = torch.softmax(z, dim=-1)
+            if "task" in kinds:
+                out[f"task_{name}_labels"], out[f"task_{name}_label_probs"] = _calls_torch(p)
+            if "task_probs" in kinds:
+                out[f"task_{name}_probs"] = p
 
     def _predict_hip(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
         from .ops import infer_heads as ih
@@ -138,12 +265,22 @@ class Predictor:
         hidden_g: List[torch.Tensor] = []
         hidden_p: List[torch.Tensor] = []
 
-        def tap(i, h_i, g_i):
-            hidden_g.append(g_i)
-            hidden_p.append(ih.masked_mean_pool(h_i.contiguous(), tokens))      # one pool launch per block
-
+        hs_all: List[torch.Tensor] = []       # references to every block's states, as _FinetuneBase._encode_all
+        gs_all: List[torch.Tensor] = []
         want_hidden = "hidden_states" in outputs
-        h, g, g_bf = fused_encode(model, tokens, ann, return_bf16=True, tap=tap if want_hidden else None)
+        req = self._task_requests(outputs)
+        want_all = self._needs_all(req)
+
+        def tap(i, h_i, g_i):
+            if want_all:
+                hs_all.append(h_i)
+                gs_all.append(g_i)
+            if want_hidden:
+                hidden_g.append(g_i)
+                hidden_p.append(ih.masked_mean_pool(h_i.contiguous(), tokens))  # one pool launch per block
+
+        h, g, g_bf = fused_encode(model, tokens, ann, return_bf16=True,
+                                  tap=tap if (want_hidden or want_all) else None)
         h = h.contiguous()
         out: Dict[str, torch.Tensor] = {}
         if "global" in outputs:
@@ -169,6 +306,7 @@ class Predictor:
         if want_hidden:
             out["hidden_global"] = torch.stack(hidden_g, dim=1)
             out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
+        self._task_outputs(out, req, tokens, h, g, hs_all, gs_all, hip=True)
         return out
 
     def _predict_torch(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
@@ -176,12 +314,21 @@ class Predictor:
         hidden_g: List[torch.Tensor] = []
         hidden_p: List[torch.Tensor] = []
 
-        def tap(i, h_i, g_i):
-            hidden_g.append(g_i.float())
-            hidden_p.append(masked_mean_torch(h_i, tokens))
-
+        hs_all: List[torch.Tensor] = []
+        gs_all: List[torch.Tensor] = []
         want_hidden = "hidden_states" in outputs
-        h, g = model.encode_torch(tokens, ann, tap=tap if want_hidden else None)
+        req = self._task_requests(outputs)
+        want_all = self._needs_all(req)
+
+        def tap(i, h_i, g_i):
+            if want_all:
+                hs_all.append(h_i)
+                gs_all.append(g_i)
+            if want_hidden:
+                hidden_g.append(g_i.float())
+                hidden_p.append(masked_mean_torch(h_i, tokens))
+
+        h, g = model.encode_torch(tokens, ann, tap=tap if (want_hidden or want_all) else None)
         out: Dict[str, torch.Tensor] = {}
         if "global" in outputs:
             out["global"] = g.float()
@@ -205,6 +352,7 @@ class Predictor:
         if want_hidden:
             out["hidden_global"] = torch.stack(hidden_g, dim=1)
             out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
+        self._task_outputs(out, req, tokens, h, g, hs_all, gs_all, hip=False)
         return out
 
     # ------------------------------------------------------------------------
@@ -215,7 +363,7 @@ class Predictor:
         tensor ``[N, L]``, taken as it is) in batches of ``batch_size``: CPU tensors in input order.  No host
         synchronisation per batch: every batch's outputs are copied, without blocking, into host tensors
         allocated once (pinned when the model is on a GPU), and the device is synchronised once at the end."""
-        outputs = _check_outputs(outputs)
+        outputs = _check_outputs(outputs, self.heads)
         tokens = sequences if isinstance(sequences, torch.Tensor) else self.tokenize(list(sequences), truncate)
         if tokens.dim() != 2 or tokens.dtype != torch.int64:
             raise ValueError("token input must be an int64 [N, L] tensor")

@@ -164,3 +164,28 @@ class ProteinBERTForSequenceClassification(_FinetuneBase):
             return self.head(self.dropout(torch.cat([g.float() for g in gs], dim=-1)))
         _, g = self._encode(x)
         return self.head(self.dropout(g.float()))
+
+
+def build_finetune_model(enc: ProteinBERT, meta: dict, freeze_encoder: bool = True):
+    """The head class a saved head file's ``meta`` describes (:func:`load_finetuned_head`)."""
+    if meta["task"] == "residue":
+        return ProteinBERTForTokenClassification(enc, n_classes=meta["n_classes"], freeze_encoder=freeze_encoder,
+                                                 use_global=meta["use_global"], hidden=meta["hidden"])
+    return ProteinBERTForSequenceClassification(enc, n_classes=meta["n_classes"], freeze_encoder=freeze_encoder,
+                                                hidden=meta["hidden"])
+
+
+def load_finetuned_head(path: str, enc: ProteinBERT, freeze_encoder: bool = True):
+    """Rebuild the fine-tuned model of a ``proteinbert_finetuned_head.pt`` around ``enc``.  The file's ``"meta"``
+    entry names the task and head form; a file without it is a ``hidden="last"`` per-residue head."""
+    state = dict(torch.load(path, map_location="cpu"))
+    meta = state.pop("meta", None)
+    if meta is None:
+        meta = {"task": "residue", "hidden": "last", "n_classes": state["head.weight"].shape[0], "classes": None,
+                "use_global": "global_head.weight" in state}
+    model = build_finetune_model(enc, meta, freeze_encoder)
+    missing, unexpected = model.load_state_dict(state, strict=False)
+    if unexpected or any(not k.startswith("encoder.") for k in missing):
+        raise ValueError(f"{path}: head does not fit meta {meta}: missing "
+                         f"{[k for k in missing if not k.startswith('encoder.')]}, unexpected {unexpected}")
+    return model, meta

@@ -295,6 +295,137 @@ __global__ void __launch_bounds__(256) token_head_multi_wgrad_kernel(const Multi
   }
 }
 
+// ---- prediction with a trained per-residue head: calls and probabilities instead of logits ----
+//   z[m][k] = b[k] + sum_i sum_c h_i[m][c] W[k][i * 128 + c]  (+ gterm[m / L][k])
+//   P[m][k] = exp(z[m][k] - max_k z) / sum_k exp(z[m][k] - max_k z)
+//   label[m] = the lowest k whose computed P[m][k] is maximal, pmax[m] = that P
+// Staging, prefetch and FMA order are token_head_multi_fwd_kernel's, statement for statement (one 64 KiB LDS
+// image, the next block in registers, blocks ascending, gterm last), so the logits a thread holds after the
+// block walk are bit for bit the ones that kernel stores; they never leave the registers.  The epilogue is
+// K values per thread: row maximum, __expf, the sum in ascending k, one division per class, and a strict >
+// scan in ascending k (pbx_phead_probs' rule: the call is exact on the probabilities as computed).  A row whose
+// token is below min_token holds no residue (<pad>, <sos>, <eos>): label -1, pmax 0 and a zero probability row;
+// its FMAs are skipped (a wave of pads costs only the staging).  Rows >= M are neither read nor written.
+template <int K>
+__global__ void __launch_bounds__(256) token_head_calls_kernel(const MultiSrc src, const int nb,
+                                                               const float* __restrict__ W,
+                                                               const float* __restrict__ b,
+                                                               const float* __restrict__ gterm,
+                                                               const long long* __restrict__ tokens,
+                                                               const int min_token, float* __restrict__ probs,
+                                                               int* __restrict__ labels, float* __restrict__ pmax,
+                                                               long M, int L) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 256 rows x 256 B
+  __shared__ float ws[K * CH];
+  const long m0 = (long)blockIdx.x * 256;
+  const int n = (int)min((long)256, M - m0);
+  const int row = threadIdx.x;
+  const int ldw = nb * CH;
+  // the token is needed only after the block walk: issued first, its latency is behind the first staging
+  const bool live = row < n && (tokens == nullptr || tokens[m0 + row] >= (long long)min_token);
+  float acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = b[k];
+  uint4 pre[16];                             // chunk idx = tid + 256 j of block i: row idx >> 4, 16-B chunk idx & 15
+  auto fetch = [&](int i) {
+    const bf16_t* __restrict__ h = src.p[i];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      pre[j] = (idx >> 4) < n ? *reinterpret_cast<const uint4*>(h + (m0 + (idx >> 4)) * CH + (idx & 15) * 8)
+                              : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  auto stage = [&](int i) {                  // the fetched rows (swz256: conflict-free row reads) + W[:, block i]
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      *reinterpret_cast<uint4*>(smem + swz256(idx >> 4, idx & 15)) = pre[j];
+    }
+    for (int j = threadIdx.x; j < K * CH; j += 256) ws[j] = W[(j >> 7) * ldw + i * CH + (j & (CH - 1))];
+  };
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int i = 0; i < nb; ++i) {
+    if (i + 1 < nb) fetch(i + 1);
+    if (live) {
+#pragma unroll 4
+      for (int c = 0; c < 16; ++c) {
+        float v[8];
+        unpack8(*reinterpret_cast<const uint4*>(smem + swz256(row, c)), v);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float* wr = ws + k * CH + c * 8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[k] = fmaf(v[e], wr[e], acc[k]);
+        }
+      }
+    }
+    if (i + 1 < nb) {
+      __syncthreads();                       // every thread is done with block i's image
+      stage(i + 1);
+      __syncthreads();
+    }
+  }
+  if (row >= n) return;
+  float* pr = probs != nullptr ? probs + (m0 + row) * K : nullptr;
+  if (!live) {
+    labels[m0 + row] = -1;
+    pmax[m0 + row] = 0.f;
+    if (pr != nullptr) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) pr[k] = 0.f;
+    }
+    return;
+  }
+  if (gterm != nullptr) {
+    const float* gt = gterm + ((m0 + row) / L) * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] += gt[k];
+  }
+  float mx = acc[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) mx = fmaxf(mx, acc[k]);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    acc[k] = __expf(acc[k] - mx);
+    s += acc[k];
+  }
+  float bv = -1.f;
+  int bi = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {              // k ascending: a strict > keeps the lowest index
+    acc[k] = acc[k] / s;
+    if (acc[k] > bv) {
+      bv = acc[k];
+      bi = k;
+    }
+  }
+  labels[m0 + row] = bi;
+  pmax[m0 + row] = bv;
+  if (pr != nullptr) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) pr[k] = acc[k];
+  }
+}
+
+template <int K>
+int token_head_calls_launch(const MultiSrc& src, int nb, const float* W, const float* b, const float* gterm,
+                            const long long* tokens, int min_token, float* probs, int* labels, float* pmax, long M,
+                            int L, hipStream_t st) {
+  static bool attr = false;                  // 64 KiB dynamic + the static weight slice exceed the default
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)token_head_calls_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              256 * 256);
+    attr = true;
+  }
+  hipLaunchKernelGGL(token_head_calls_kernel<K>, dim3((unsigned)((M + 255) / 256)), dim3(256), 256 * 256, st, src,
+                     nb, W, b, gterm, tokens, min_token, probs, labels, pmax, M, L);
+  return pbx_launch_status();
+}
+
 bool multi_src(const void* const* srcs, int nb, MultiSrc& ms) {
   if (srcs == nullptr || nb < 1 || nb > MAXSRC) return false;
   for (int i = 0; i < MAXSRC; ++i) {
@@ -330,6 +461,28 @@ PBX_EXPORT int pbx_token_head_multi_fwd(const void* const* srcs, int nb, const f
     case 16: return token_head_multi_fwd_launch<16>(ms, nb, W, b, gterm, out, M, L, st);
     default: return (int)hipErrorInvalidValue;
   }
+}
+
+// Prediction with a per-residue head: operands as pbx_token_head_multi_fwd (nb = 1 without gterm: those of
+// pbx_token_head_fwd) -> labels [M] int32, pmax [M] fp32 and, unless probs is null, probs [M][K] fp32 =
+// softmax over the K classes; the logits are not written.  tokens ([M] int64, may be null): a row whose token is
+// below min_token gets label -1, pmax 0 and a zero probability row.  No atomics: bitwise repeatable.
+PBX_EXPORT int pbx_token_head_calls(const void* const* srcs, int nb, const float* W, const float* b,
+                                    const float* gterm, const long long* tokens, int min_token, float* probs,
+                                    int* labels, float* pmax, long M, int K, int L, hipStream_t st) {
+  MultiSrc ms;
+  if (M < 1 || L < 1 || labels == nullptr || pmax == nullptr || !multi_src(srcs, nb, ms))
+    return (int)hipErrorInvalidValue;
+#define PBX_CALLS_CASE(KK) \
+  case KK: return token_head_calls_launch<KK>(ms, nb, W, b, gterm, tokens, min_token, probs, labels, pmax, M, L, st);
+  switch (K) {
+    PBX_CALLS_CASE(1) PBX_CALLS_CASE(2) PBX_CALLS_CASE(3) PBX_CALLS_CASE(4)
+    PBX_CALLS_CASE(5) PBX_CALLS_CASE(6) PBX_CALLS_CASE(7) PBX_CALLS_CASE(8)
+    PBX_CALLS_CASE(9) PBX_CALLS_CASE(10) PBX_CALLS_CASE(11) PBX_CALLS_CASE(12)
+    PBX_CALLS_CASE(13) PBX_CALLS_CASE(14) PBX_CALLS_CASE(15) PBX_CALLS_CASE(16)
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef PBX_CALLS_CASE
 }
 
 // slab: [P][K][nb*128] fp32 partials (P = number of workgroups, chosen by the caller); srcs as above; K <= 16

@@ -9,17 +9,22 @@ counts; neither returns a prediction.  Here each head writes what :mod:`..infere
   order (``torch.sort(descending=True, stable=True)[:k]``), one wave per row with the row in registers;
 * :func:`local_probs` -- the local head of either semantics: optional probabilities ``[B, L, V]``, the called
   token of every position (the lowest index of the maximum of the stored probabilities) and its probability;
-* :func:`masked_mean_pool` -- the mean of ``h`` over the non-``<pad>`` positions.
+* :func:`masked_mean_pool` -- the mean of ``h`` over the non-``<pad>`` positions;
+* :func:`token_head_calls` -- a fine-tuned per-residue task head (``csrc/finetune.hip``): the class of every
+  residue, its probability and optionally the class probabilities, from 1..8 row sources in one launch whose
+  logits stay in registers.
 
 No autograd Function is involved, nothing is kept for a backward pass, and every output is bitwise repeatable.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, finetune_head
+from ..data.vocab import UNK_ID
+from .finetune_head import MAX_SOURCES
 from .global_track import bf16_of
 
 F32 = torch.float32
@@ -81,7 +86,7 @@ def _probs_out(out: Optional[torch.Tensor], store_probs: bool, B: int, L: int, V
     if out is None:
         return torch.empty((B, L, V), dtype=F32, device=dev)
     if out.shape != (B, L, V) or out.dtype != F32 or not out.is_contiguous():
-        raise ValueError(f"local probabilities: out must be a contiguous fp32 [{B}, {L}, {V}] tensor")
+        raise ValueError(f"probabilities: out must be a contiguous fp32 [{B}, {L}, {V}] tensor")
     return out
 
 
@@ -134,6 +139,84 @@ def local_probs(model, h: torch.Tensor, store_probs: bool = True):
     lo = model.pretraining_local_output[0]
     fn = local_probs_paper if model.semantics == "paper" else local_probs_ref
     return fn(h, lo.weight, lo.bias, store_probs)
+
+
+def _task_head_args(hs: Sequence[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor,
+                    gterm: Optional[torch.Tensor], tokens: Optional[torch.Tensor]) -> Tuple[int, int, int]:
+    """``(B, L, K)`` of a task-head call, or ``ValueError``: shapes only, so it holds on any device."""
+    if not 1 <= len(hs) <= MAX_SOURCES:
+        raise ValueError(f"token_head_calls: {len(hs)} row sources: expected 1 .. {MAX_SOURCES}")
+    h0 = hs[0]
+    if any(h.dim() != 3 or h.shape != h0.shape or h.device != h0.device or h.dtype != h0.dtype for h in hs):
+        raise ValueError("token_head_calls: the sources must be [B, L, C] tensors of one shape, dtype and device")
+    B, L, C = h0.shape
+    if B < 1 or L < 1:
+        raise ValueError("token_head_calls: empty sources")
+    K = weight.shape[0] if weight.dim() == 2 else 0
+    if not 1 <= K <= 16:
+        raise ValueError(f"token_head_calls: weight {tuple(weight.shape)}: expected [K, {len(hs) * C}], 1 <= K <= 16")
+    if weight.shape[1] != len(hs) * C:
+        raise ValueError(f"token_head_calls: weight {tuple(weight.shape)} for {len(hs)} sources of {C} channels")
+    if tuple(bias.shape) != (K,):
+        raise ValueError(f"token_head_calls: bias {tuple(bias.shape)}: expected {(K,)}")
+    if gterm is not None and tuple(gterm.shape) != (B, K):
+        raise ValueError(f"token_head_calls: gterm {tuple(gterm.shape)}: expected {(B, K)}")
+    if tokens is not None and (tuple(tokens.shape) != (B, L) or tokens.dtype != torch.int64):
+        raise ValueError(f"token_head_calls: tokens must be int64 {(B, L)}")
+    return B, L, K
+
+
+def token_head_calls(hs: Sequence[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor,
+                     gterm: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+                     store_probs: bool = False, out: Optional[torch.Tensor] = None, min_token: int = UNK_ID):
+    """Prediction with a per-residue task head (``pbx_token_head_calls``, one launch): ``hs``: 1..8 bf16
+    ``[B, L, 128]`` row sources (the last block's state, or every block's for ``hidden="all"``), ``weight``
+    ``[K, nb*128]``, ``bias`` ``[K]``, ``gterm`` ``[B, K]`` (the global term, added last), ``K <= 16``.  Returns
+    ``(P [B, L, K] fp32 or None, labels [B, L] int32, pmax [B, L] fp32)``: the softmax over the classes of the
+    logits :class:`.finetune_head.MultiTokenHeadFn` would store (they are never written), the lowest class of
+    maximal stored probability and that probability.  With ``tokens`` ``[B, L]`` int64 a position whose token is
+    below ``min_token`` (``<pad>``, ``<sos>``, ``<eos>``) gets label -1, probability 0 and a zero row.  ``out``: a
+    contiguous fp32 ``[B, L, K]`` tensor to write ``P`` into.  Everything is validated before the launch."""
+    B, L, K = _task_head_args(hs, weight, bias, gterm, tokens)
+    if not finetune_head.supported_multi(hs, K):
+        raise ValueError("token_head_calls: the sources must be CUDA bf16 [B, L, 128] tensors "
+                         "(token_head_calls_torch is the definition on any device)")
+    dev = hs[0].device
+    P = _probs_out(out, store_probs, B, L, K, dev)
+    rows = [finetune_head._rows(h) for h in hs]
+    w32 = weight.detach().float().contiguous()
+    b32 = bias.detach().float().contiguous()
+    gt = None if gterm is None else gterm.detach().float().contiguous()
+    tk = None if tokens is None else tokens.contiguous()
+    labels = torch.empty((B, L), dtype=torch.int32, device=dev)
+    pmax = torch.empty((B, L), dtype=F32, device=dev)
+    _lib.call("pbx_token_head_calls", finetune_head._src_array(rows), len(rows), w32.data_ptr(), b32.data_ptr(),
+              _lib.ptr(gt), _lib.ptr(tk), int(min_token), _lib.ptr(P), labels.data_ptr(), pmax.data_ptr(), B * L, K, L,
+              _s(dev))
+    return P, labels, pmax
+
+
+def token_head_calls_torch(hs: Sequence[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor,
+                           gterm: Optional[torch.Tensor] = None, tokens: Optional[torch.Tensor] = None,
+                           store_probs: bool = False, out: Optional[torch.Tensor] = None, min_token: int = UNK_ID):
+    """:func:`token_head_calls` by definition, on any device and for any channel count: fp32
+    ``softmax(Linear(cat_i h_i) + gterm)`` over the classes, the first maximal index of the probabilities as
+    computed (``argmax``), label -1 / zeros at the masked positions."""
+    B, L, K = _task_head_args(hs, weight, bias, gterm, tokens)
+    P = _probs_out(out, store_probs, B, L, K, hs[0].device)
+    probs = torch.softmax(finetune_head.multi_head_torch(hs, weight.detach().float(), bias.detach().float(),
+                                                         None if gterm is None else gterm.detach().float()), dim=-1)
+    labels = probs.argmax(dim=-1)
+    pmax = probs.gather(-1, labels.unsqueeze(-1)).squeeze(-1)
+    labels = labels.to(torch.int32)
+    if tokens is not None:
+        live = tokens >= min_token
+        labels = torch.where(live, labels, torch.full_like(labels, -1))
+        pmax = pmax * live
+        probs = probs * live.unsqueeze(-1)
+    if P is not None:
+        P.copy_(probs)
+    return P, labels, pmax
 
 
 def masked_mean_pool(h: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
