@@ -7,6 +7,7 @@ COMMANDS = {
     "pretrain": ("train", "pretrain_main"),
     "finetune": ("train", "finetune_main"),
     "predict": ("predict", "main"),
+    "evaluate": ("evaluate", "main"),
     "dummy-tests": ("dummy_tests", "main"),
 }
 

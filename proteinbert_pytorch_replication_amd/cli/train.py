@@ -17,6 +17,11 @@ loss and the test set's Spearman correlation per epoch.  ``--hidden all`` puts t
 state instead of the last block's (:mod:`..models.finetune`).  The head is saved as
 ``proteinbert_finetuned_head.pt`` (``"head"`` in the printed JSON); ``--unfreeze`` also saves the encoder it
 trained as a model file (``"encoder"``), the pair ``cli predict --model ... --head NAME=...`` takes.
+``--eval exact`` evaluates the test set per epoch with whole-set sums, the confusion matrix and per-class metrics
+(:mod:`..train.evaluate_finetune`) instead of the mean of per-batch values; ``--select-metric NAME`` then saves
+the head of the epoch that is best by that scalar and ``--patience N`` stops after N epochs without improvement
+(``"test_eval"`` and ``"best_epoch"`` in the printed JSON).  ``cli evaluate`` (:mod:`.evaluate`) reports the same
+metrics for a saved head.
 """
 from __future__ import annotations
 
@@ -226,6 +231,13 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
     ap.add_argument("--hidden", default="last", choices=("last", "all"),
                     help="head input: the last block's hidden state, or every block's, concatenated")
     ap.add_argument("--n-classes", type=int, default=2, help="--task sequence: number of classes")
+    ap.add_argument("--eval", default="batch-mean", choices=("batch-mean", "exact"), dest="eval_mode",
+                    help="test-set evaluation per epoch: the mean of per-batch values, or exact whole-set sums "
+                         "with the confusion matrix and per-class metrics")
+    ap.add_argument("--select-metric", default=None,
+                    help="with --eval exact: keep the epoch that is best by this scalar (e.g. macro_f1, loss)")
+    ap.add_argument("--patience", type=int, default=None,
+                    help="with --select-metric: stop after this many epochs without improvement")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(format="%(asctime)s [%(levelname)s]: %(message)s", level=logging.INFO)
@@ -302,6 +314,11 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
     else:
         # Spearman is a statistic of the whole test set, computed once per epoch, not a mean over batches
         task_args = dict(metrics={}, loss_fn=regression_loss(), epoch_metrics={"spearman": spearman})
+    if a.eval_mode == "exact":
+        # the selected epoch's parameters are back in the model when finetune returns: the files below hold them
+        task_args.update(evaluate="exact", select_metric=a.select_metric, patience=a.patience)
+    elif a.select_metric is not None or a.patience is not None:
+        raise ValueError("--select-metric / --patience need --eval exact")
     res = finetune(model, dl, opt, epochs=a.epochs, test_dataloader=tl, device=dev, ddp=ddp, log=print, **task_args)
     res["optimizer"] = opt
     res["meta"] = meta
@@ -317,6 +334,9 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
         torch.save(head, path)
         res["head"] = path
         summary = {"train_loss": res["train_loss"], "test_metrics": res["test_metrics"], "head": path}
+        if a.eval_mode == "exact":
+            summary["test_eval"] = res["test_metrics"][-1] if res["test_metrics"] else None
+            summary["best_epoch"] = res.get("best_epoch")
         if a.unfreeze:
             # the head file holds no encoder entries: without the encoder it was trained with, the head could
             # never be used (inference.Predictor(load_model(encoder), heads={...: head file}))

@@ -426,6 +426,215 @@ int token_head_calls_launch(const MultiSrc& src, int nb, const float* W, const f
   return pbx_launch_status();
 }
 
+// ---- evaluation of a trained per-residue head: cross-entropy and a K x K confusion table instead of calls ----
+//   z[m][k] as above;  call[m] = token_head_calls_kernel's label;  ce[m] = log sum_k exp(z - max z) - (z_y - max z)
+// Staging, prefetch and FMA order are token_head_calls_kernel's, statement for statement, so the logits a thread
+// holds are bit for bit that kernel's (and token_head_multi_fwd_kernel's) and its call is that kernel's label.
+// Row classes by the label y[m]: y < 0 is ignored (the -100 of the loaders; its FMAs are skipped), y >= K is a
+// bad label (counted in slot K*K + 1, otherwise ignored), every other row is live: one LDS integer atomic on
+// cm[y * K + call], one on the live-row count (slot K*K).  Workgroup w owns rows 256 w .. 256 w + 255 and writes
+// loss_part[w] (lane-ordered wave reduction, then waves 0..3 in order: no float atomics, bitwise repeatable) and
+// cnt_part[w][K*K + 2].  The LDS image grows by the table alone (<= 1032 B): two workgroups still fit a CU.
+// Rows >= M are neither read nor counted; the logits are never written.
+template <int K>
+__global__ void __launch_bounds__(256) token_head_eval_kernel(const MultiSrc src, const int nb,
+                                                              const float* __restrict__ W,
+                                                              const float* __restrict__ b,
+                                                              const float* __restrict__ gterm,
+                                                              const long long* __restrict__ y,
+                                                              float* __restrict__ loss_part,
+                                                              unsigned* __restrict__ cnt_part, long M, int L) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 256 rows x 256 B
+  __shared__ float ws[K * CH];
+  constexpr int NC = K * K + 2;
+  __shared__ unsigned cm[NC];
+  __shared__ float wsum[4];
+  const long m0 = (long)blockIdx.x * 256;
+  const int n = (int)min((long)256, M - m0);
+  const int row = threadIdx.x;
+  const int ldw = nb * CH;
+  // the label is needed only after the block walk: issued first, its latency is behind the first staging
+  const long long yv = row < n ? y[m0 + row] : -1ll;
+  const bool live = yv >= 0 && yv < (long long)K;
+  for (int j = threadIdx.x; j < NC; j += 256) cm[j] = 0u;     // visible after the first staging barrier
+  float acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = b[k];
+  uint4 pre[16];                             // chunk idx = tid + 256 j of block i: row idx >> 4, 16-B chunk idx & 15
+  auto fetch = [&](int i) {
+    const bf16_t* __restrict__ h = src.p[i];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      pre[j] = (idx >> 4) < n ? *reinterpret_cast<const uint4*>(h + (m0 + (idx >> 4)) * CH + (idx & 15) * 8)
+                              : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  auto stage = [&](int i) {                  // the fetched rows (swz256: conflict-free row reads) + W[:, block i]
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      *reinterpret_cast<uint4*>(smem + swz256(idx >> 4, idx & 15)) = pre[j];
+    }
+    for (int j = threadIdx.x; j < K * CH; j += 256) ws[j] = W[(j >> 7) * ldw + i * CH + (j & (CH - 1))];
+  };
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int i = 0; i < nb; ++i) {
+    if (i + 1 < nb) fetch(i + 1);
+    if (live) {
+#pragma unroll 4
+      for (int c = 0; c < 16; ++c) {
+        float v[8];
+        unpack8(*reinterpret_cast<const uint4*>(smem + swz256(row, c)), v);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float* wr = ws + k * CH + c * 8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[k] = fmaf(v[e], wr[e], acc[k]);
+        }
+      }
+    }
+    if (i + 1 < nb) {
+      __syncthreads();                       // every thread is done with block i's image
+      stage(i + 1);
+      __syncthreads();
+    }
+  }
+  float ce = 0.f;                            // no early return: every thread reaches the barriers below
+  if (live) {
+    if (gterm != nullptr) {
+      const float* gt = gterm + ((m0 + row) / L) * K;
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] += gt[k];
+    }
+    const int yi = (int)yv;
+    float mx = acc[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, acc[k]);
+    float s = 0.f, zy = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      zy = k == yi ? acc[k] - mx : zy;
+      acc[k] = __expf(acc[k] - mx);
+      s += acc[k];
+    }
+    float bv = -1.f;
+    int bi = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {            // k ascending: a strict > keeps the lowest index
+      acc[k] = acc[k] / s;
+      if (acc[k] > bv) {
+        bv = acc[k];
+        bi = k;
+      }
+    }
+    ce = logf(s) - zy;
+    atomicAdd(&cm[yi * K + bi], 1u);
+    atomicAdd(&cm[K * K], 1u);
+  } else if (yv >= (long long)K) {
+    atomicAdd(&cm[K * K + 1], 1u);
+  }
+  ce = wave_reduce_sum(ce);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ce;
+  __syncthreads();                           // the table and the four wave sums are complete
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  unsigned* cp = cnt_part + (size_t)blockIdx.x * NC;
+  for (int j = threadIdx.x; j < NC; j += 256) cp[j] = cm[j];
+}
+
+template <int K>
+int token_head_eval_launch(const MultiSrc& src, int nb, const float* W, const float* b, const float* gterm,
+                           const long long* y, float* loss_part, unsigned* cnt_part, long M, int L, hipStream_t st) {
+  static bool attr = false;                  // 64 KiB dynamic + the static weight slice and table exceed the default
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)token_head_eval_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              256 * 256);
+    attr = true;
+  }
+  hipLaunchKernelGGL(token_head_eval_kernel<K>, dim3((unsigned)((M + 255) / 256)), dim3(256), 256 * 256, st, src, nb,
+                     W, b, gterm, y, loss_part, cnt_part, M, L);
+  return pbx_launch_status();
+}
+
+// ---- fold: one batch's partials of token_head_eval_kernel -> the persistent accumulator (eval_fold_kernel's
+// scheme, csrc/evalhead.hip).  Block (0, 0): the loss partials in fp64, ascending workgroup order at every level:
+// thread t adds the contiguous run t * run .. (t + 1) * run - 1 (run = ceil(nwg / 256): one partial each up to 256
+// workgroups; four loads in flight), threads 0..15 add the run sums 16 t .. 16 t + 15, thread 0 adds those 16
+// (a single thread walking all 256 run sums made the fold a fifth of the head itself at 4096 workgroups); and the
+// batch / sequence counters.  Blocks (1 .., s): 16 columns of the [nwg][K*K + 2] table each over the s-th of
+// gridDim.y row ranges, the rows split over 16 thread groups with four loads in flight per thread; a block adds
+// its column sums to the accumulator with 64-bit integer atomics (integers: exact in any order, so the result
+// is the same on every launch).  No float atomics.
+//   acc_loss [1] fp64;  acc_cnt [K*K + 4] int64: confusion [K][K] (true x predicted), live rows, bad labels,
+//   batches, sequences
+__global__ void __launch_bounds__(256) task_eval_fold_kernel(const float* __restrict__ loss_part,
+                                                             const unsigned* __restrict__ cnt_part, int nwg, int nc,
+                                                             int n_sequences, double* __restrict__ acc_loss,
+                                                             long long* __restrict__ acc_cnt) {
+  __shared__ double dred[256];
+  __shared__ double dred2[16];
+  __shared__ unsigned long long ured[16][16];
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0) {
+    if (blockIdx.y != 0) return;
+    const int run = (nwg + 255) / 256;
+    const int i1 = min(nwg, (tid + 1) * run);
+    int i = min(nwg, tid * run);
+    double a = 0.0;
+    for (; i + 3 < i1; i += 4) {
+      const float v0 = loss_part[i], v1 = loss_part[i + 1], v2 = loss_part[i + 2], v3 = loss_part[i + 3];
+      a += (double)v0;
+      a += (double)v1;
+      a += (double)v2;
+      a += (double)v3;
+    }
+    for (; i < i1; ++i) a += (double)loss_part[i];
+    dred[tid] = a;
+    __syncthreads();
+    if (tid < 16) {
+      double s = dred[tid * 16];
+#pragma unroll
+      for (int t = 1; t < 16; ++t) s += dred[tid * 16 + t];
+      dred2[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double s = dred2[0];
+#pragma unroll
+      for (int t = 1; t < 16; ++t) s += dred2[t];
+      acc_loss[0] += s;
+      acc_cnt[nc] += 1;
+      acc_cnt[nc + 1] += n_sequences;
+    }
+    return;
+  }
+  const int cl = tid & 15, rg = tid >> 4;
+  const int col = (blockIdx.x - 1) * 16 + cl;
+  const int chunk = (nwg + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int r0 = (int)blockIdx.y * chunk, r1 = min(nwg, r0 + chunk);
+  unsigned long long s = 0ull;
+  if (col < nc) {
+    const unsigned* src = cnt_part + col;
+    int i = r0 + rg;
+    for (; i + 48 < r1; i += 64) {
+      const unsigned a = src[(size_t)i * nc], b = src[(size_t)(i + 16) * nc], c = src[(size_t)(i + 32) * nc],
+                     d = src[(size_t)(i + 48) * nc];
+      s += (unsigned long long)a + b + c + d;
+    }
+    for (; i < r1; i += 16) s += src[(size_t)i * nc];
+  }
+  ured[rg][cl] = s;
+  __syncthreads();
+  if (rg == 0 && col < nc) {
+    unsigned long long t = 0ull;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t += ured[k][cl];
+    if (t != 0ull) atomicAdd(reinterpret_cast<unsigned long long*>(acc_cnt + col), t);
+  }
+}
+
 bool multi_src(const void* const* srcs, int nb, MultiSrc& ms) {
   if (srcs == nullptr || nb < 1 || nb > MAXSRC) return false;
   for (int i = 0; i < MAXSRC; ++i) {
@@ -483,6 +692,48 @@ PBX_EXPORT int pbx_token_head_calls(const void* const* srcs, int nb, const float
     default: return (int)hipErrorInvalidValue;
   }
 #undef PBX_CALLS_CASE
+}
+
+// Workgroups of pbx_token_head_eval on M rows (workgroup w owns rows 256 w .. 256 w + 255): the partial rows it writes.
+PBX_EXPORT int pbx_token_head_eval_parts(long M) {
+  return M < 1 ? 0 : (int)((M + 255) / 256);
+}
+
+// Evaluation of a per-residue head: operands as pbx_token_head_calls with y ([M] int64 labels: y < 0 ignored,
+// y >= K counted as a bad label) in place of the tokens -> loss_part [nwg] fp32 (the workgroup's sum of the live
+// rows' cross-entropy) and cnt_part [nwg][K*K + 2] uint32 (confusion true x predicted, live rows, bad labels),
+// nwg = pbx_token_head_eval_parts(M).  The logits are not written.  Integer LDS atomics only: bitwise repeatable.
+PBX_EXPORT int pbx_token_head_eval(const void* const* srcs, int nb, const float* W, const float* b,
+                                   const float* gterm, const long long* y, float* loss_part, unsigned* cnt_part,
+                                   long M, int K, int L, hipStream_t st) {
+  MultiSrc ms;
+  if (M < 1 || L < 1 || W == nullptr || b == nullptr || y == nullptr || loss_part == nullptr || cnt_part == nullptr ||
+      !multi_src(srcs, nb, ms))
+    return (int)hipErrorInvalidValue;
+#define PBX_EVAL_CASE(KK) \
+  case KK: return token_head_eval_launch<KK>(ms, nb, W, b, gterm, y, loss_part, cnt_part, M, L, st);
+  switch (K) {
+    PBX_EVAL_CASE(1) PBX_EVAL_CASE(2) PBX_EVAL_CASE(3) PBX_EVAL_CASE(4)
+    PBX_EVAL_CASE(5) PBX_EVAL_CASE(6) PBX_EVAL_CASE(7) PBX_EVAL_CASE(8)
+    PBX_EVAL_CASE(9) PBX_EVAL_CASE(10) PBX_EVAL_CASE(11) PBX_EVAL_CASE(12)
+    PBX_EVAL_CASE(13) PBX_EVAL_CASE(14) PBX_EVAL_CASE(15) PBX_EVAL_CASE(16)
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef PBX_EVAL_CASE
+}
+
+// One batch's partials of pbx_token_head_eval into the accumulator: acc_loss [1] fp64, acc_cnt [K*K + 4] int64
+// (confusion, live rows, bad labels, batches, sequences); one launch, fixed summation order.
+PBX_EXPORT int pbx_task_eval_fold(const float* loss_part, const unsigned* cnt_part, int nwg, int K, int n_sequences,
+                                  double* acc_loss, long long* acc_cnt, hipStream_t st) {
+  if (loss_part == nullptr || cnt_part == nullptr || acc_loss == nullptr || acc_cnt == nullptr || nwg < 1 || K < 1 ||
+      K > 16 || n_sequences < 0)
+    return (int)hipErrorInvalidValue;
+  const int nc = K * K + 2;
+  const int rs = nwg >= 16 * 256 ? 16 : (nwg + 255) / 256;     // row ranges of <= 256 partial rows, at most 16 of them
+  hipLaunchKernelGGL(task_eval_fold_kernel, dim3(1 + (nc + 15) / 16, rs), dim3(256), 0, st, loss_part, cnt_part, nwg,
+                     nc, n_sequences, acc_loss, acc_cnt);
+  return pbx_launch_status();
 }
 
 // slab: [P][K][nb*128] fp32 partials (P = number of workgroups, chosen by the caller); srcs as above; K <= 16

@@ -161,20 +161,55 @@ def spearman(pred: torch.Tensor, y: torch.Tensor) -> float:
     return float((rp * rt).sum() / den) if den > 0 else 0.0
 
 
+EVALUATE_MODES = ("batch_mean", "exact")
+SMALLER_IS_BETTER = ("loss", "mse", "mae")
+
+
 def finetune(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Optimizer, epochs: int = 1,
              test_dataloader=None, loss_fn: Optional[torch.nn.Module] = None, metrics: Optional[Dict] = None,
              gradient_clipping: bool = True, gradient_clipping_thresh: float = 1.0, device=None,
              ddp=None, log: Optional[Callable[[str], None]] = None,
-             epoch_metrics: Optional[Dict[str, Callable]] = None) -> Dict[str, Any]:
+             epoch_metrics: Optional[Dict[str, Callable]] = None, evaluate: str = "batch_mean",
+             select_metric: Optional[str] = None, patience: Optional[int] = None) -> Dict[str, Any]:
     """Epoch loop around :func:`train_step` / :func:`test_step` (the shape of the reference's
     commented ``train()``, ``utils.py:348-460``).
 
     ``epoch_metrics``: ``name -> fn(outputs, y)`` evaluated once per epoch on the model's raw outputs over the
     whole test set (this rank's share of it), e.g. ``{"spearman": spearman}``: such a statistic is not a mean
-    of per-batch values.  Reported in ``results["test_metrics"]`` beside the batch-mean metrics."""
+    of per-batch values.  Reported in ``results["test_metrics"]`` beside the batch-mean metrics.
+
+    ``evaluate``: ``"batch_mean"`` (the default) is :func:`test_step`, the reference's mean of per-batch values.
+    ``"exact"`` (needs ``test_dataloader``) runs :func:`.evaluate_finetune.evaluate_finetune` per epoch instead:
+    whole-set sums, the confusion matrix and what follows from it.  ``results["test_eval"]`` gets the metric
+    dicts, ``results["test_loss"]`` their ``loss`` (``mse`` for regression) and ``results["test_metrics"]`` their
+    scalars.  Under ``ddp`` a test loader whose sampler is a :class:`..parallel.sampler.ShardedSampler` is this
+    rank's shard and the sums are all-reduced; any other test loader is evaluated whole by every rank.
+
+    ``select_metric`` (needs ``evaluate="exact"``): a scalar of those dicts; larger is better except for
+    ``loss``, ``mse`` and ``mae``, and ``nan`` never wins.  The trainable parameters of the best epoch are kept
+    as a CPU copy and loaded back after the last epoch; ``results["best_epoch"]`` (0-based) and
+    ``results["best_metric"]`` name it.  ``patience=p`` (needs ``select_metric``): stop after ``p`` epochs
+    without improvement; ``results["stopped_early"]`` records whether that happened."""
     loss_fn = loss_fn or torch.nn.CrossEntropyLoss(ignore_index=-100)
     metrics = metrics if metrics is not None else {"accuracy": token_accuracy()}
     results: Dict[str, Any] = {"train_loss": [], "test_loss": [], "train_metrics": [], "test_metrics": []}
+    if evaluate not in EVALUATE_MODES:
+        raise ValueError(f"evaluate={evaluate!r}: expected one of {EVALUATE_MODES}")
+    exact = evaluate == "exact"
+    if exact and test_dataloader is None:
+        raise ValueError('evaluate="exact" needs a test_dataloader')
+    if select_metric is not None and not exact:
+        raise ValueError('select_metric needs evaluate="exact"')
+    if patience is not None and (select_metric is None or patience < 1):
+        raise ValueError("patience needs select_metric and a value >= 1")
+    if exact:
+        from .evaluate_finetune import evaluate_finetune, scalar_metrics
+        from ..parallel.sampler import ShardedSampler
+        sharded = ddp is not None and isinstance(getattr(test_dataloader, "sampler", None), ShardedSampler)
+        results["test_eval"] = []
+        if select_metric is not None:
+            results.update(best_epoch=None, best_metric=None, stopped_early=False)
+    best_state: Optional[Dict[str, torch.Tensor]] = None
     for epoch in range(epochs):
         if hasattr(getattr(train_dataloader, "sampler", None), "set_epoch"):
             train_dataloader.sampler.set_epoch(epoch)
@@ -182,7 +217,12 @@ def finetune(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
                             gradient_clipping_thresh, device, ddp)
         results["train_loss"].append(tl)
         results["train_metrics"].append(tm)
-        if test_dataloader is not None:
+        if exact:
+            m = evaluate_finetune(model, test_dataloader, device=device, distributed=sharded)
+            results["test_eval"].append(m)
+            results["test_loss"].append(m["loss"] if "loss" in m else m["mse"])
+            results["test_metrics"].append(scalar_metrics(m))
+        elif test_dataloader is not None:
             seen: Optional[list] = [] if epoch_metrics else None
             vl, vm = test_step(model, test_dataloader, loss_fn, metrics, device, ddp is not None, collect=seen)
             if seen:
@@ -195,6 +235,25 @@ def finetune(model: torch.nn.Module, train_dataloader, optimizer: torch.optim.Op
             log(f"epoch {epoch + 1}/{epochs} train_loss={tl:.4f} {tm} "
                 + (f"test_loss={results['test_loss'][-1]:.4f} {results['test_metrics'][-1]}"
                    if test_dataloader is not None else ""))
+        if select_metric is not None:
+            if select_metric not in results["test_metrics"][-1]:
+                raise ValueError(f"select_metric={select_metric!r}: the evaluation's scalars are "
+                                 f"{sorted(results['test_metrics'][-1])}")
+            v = float(results["test_metrics"][-1][select_metric])
+            best = results["best_metric"]
+            if v == v and (best is None or (v < best if select_metric in SMALLER_IS_BETTER else v > best)):
+                results.update(best_epoch=epoch, best_metric=v)
+                best_state = {k: p.detach().to("cpu", copy=True) for k, p in model.named_parameters()
+                              if p.requires_grad}
+            elif patience is not None and epoch - (-1 if results["best_epoch"] is None
+                                                   else results["best_epoch"]) >= patience:
+                results["stopped_early"] = True
+                break
+    if best_state is not None and results["best_epoch"] != len(results["train_loss"]) - 1:
+        with torch.no_grad():
+            for k, p in model.named_parameters():
+                if k in best_state:
+                    p.copy_(best_state[k])
     return results
 
 
