@@ -22,6 +22,10 @@ trained as a model file (``"encoder"``), the pair ``cli predict --model ... --he
 the head of the epoch that is best by that scalar and ``--patience N`` stops after N epochs without improvement
 (``"test_eval"`` and ``"best_epoch"`` in the printed JSON).  ``cli evaluate`` (:mod:`.evaluate`) reports the same
 metrics for a saved head.
+``--task residue`` can shape its training loss (:mod:`..train.task_loss`): ``--class-weights balanced`` (from one
+pass over the training labels) or ``--class-weights w0,w1,...`` (one weight per class), ``--label-smoothing E``;
+``--fused-loss`` selects the same loss object with neither, i.e. the plain cross-entropy on the fused
+loss launch.  ``"loss"`` in the printed JSON records the weights and the smoothing used.
 """
 from __future__ import annotations
 
@@ -238,12 +242,32 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
                     help="with --eval exact: keep the epoch that is best by this scalar (e.g. macro_f1, loss)")
     ap.add_argument("--patience", type=int, default=None,
                     help="with --select-metric: stop after this many epochs without improvement")
+    ap.add_argument("--class-weights", default=None,
+                    help="--task residue: 'balanced' (n_live / (n_classes * count_k) over the training labels) or "
+                         "one weight per class, comma-separated")
+    ap.add_argument("--label-smoothing", type=float, default=None, help="--task residue: 0 <= E < 1")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="--task residue: the plain cross-entropy through the fused loss launch")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(format="%(asctime)s [%(levelname)s]: %(message)s", level=logging.INFO)
     info = pdist.init_distributed(backend=cfg.dist.backend)
     if a.task == "sequence" and a.n_classes < 2:
         raise ValueError("--task sequence needs --n-classes >= 2")
+    shaped = a.class_weights is not None or a.label_smoothing is not None or a.fused_loss
+    if shaped and a.task != "residue":
+        raise ValueError("--class-weights / --label-smoothing / --fused-loss need --task residue")
+    if a.label_smoothing is not None and not 0.0 <= a.label_smoothing < 1.0:
+        raise ValueError(f"--label-smoothing {a.label_smoothing}: expected 0 <= E < 1")
+    class_weights = None
+    if a.class_weights is not None and a.class_weights != "balanced":
+        try:
+            class_weights = [float(v) for v in a.class_weights.split(",")]
+        except ValueError:
+            raise ValueError(f"--class-weights {a.class_weights!r}: expected 'balanced' or w0,w1,...") from None
+        if len(class_weights) != len(a.classes):
+            raise ValueError(f"--class-weights has {len(class_weights)} weights for the {len(a.classes)} classes "
+                             f"of --classes {a.classes!r}")
     if cfg.kernel.deterministic:
         determinism.enable()
     if cfg.kernel.gelu != "fitted":
@@ -307,8 +331,18 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
         ddp.broadcast_parameters(model)
         opt.grad_scale = 1.0 / info.world_size
     from ..train.finetune import finetune, regression_loss, sequence_accuracy, spearman, token_accuracy
+    loss_info = None
     if a.task == "residue":
         task_args = dict(metrics={"accuracy": token_accuracy()})
+        if shaped:
+            from ..train.task_loss import ResidueTaskLoss, balanced_class_weights
+            if a.class_weights == "balanced":
+                # one pass over this rank's view of the training set's labels (every rank holds the whole set)
+                labels = train_ds.tensors[1] if a.train_csv else train_ds.labels
+                class_weights = balanced_class_weights(labels, n_classes).tolist()
+            task_args["loss_fn"] = ResidueTaskLoss(class_weights, a.label_smoothing or 0.0)
+            if class_weights is not None or a.label_smoothing is not None:
+                loss_info = {"class_weights": class_weights, "label_smoothing": a.label_smoothing or 0.0}
     elif a.task == "sequence":
         task_args = dict(metrics={"accuracy": sequence_accuracy()}, loss_fn=torch.nn.CrossEntropyLoss())
     else:
@@ -337,6 +371,8 @@ def finetune_main(argv: Optional[List[str]] = None) -> dict:
         if a.eval_mode == "exact":
             summary["test_eval"] = res["test_metrics"][-1] if res["test_metrics"] else None
             summary["best_epoch"] = res.get("best_epoch")
+        if loss_info is not None:
+            summary["loss"] = loss_info
         if a.unfreeze:
             # the head file holds no encoder entries: without the encoder it was trained with, the head could
             # never be used (inference.Predictor(load_model(encoder), heads={...: head file}))

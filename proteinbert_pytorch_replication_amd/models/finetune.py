@@ -147,6 +147,50 @@ class ProteinBERTForTokenClassification(_FinetuneBase):
             logits = logits + self.global_head(g.float()).unsqueeze(1)
         return logits.permute(0, 2, 1)                                                   # [B, K, L]
 
+    def loss(self, x: Inputs, y: torch.Tensor, loss) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(loss, accuracy)`` of one training batch under ``loss``, a
+        :class:`..train.task_loss.ResidueTaskLoss`: ``loss(self(x), y)`` and the accuracy of
+        :func:`..train.finetune.token_accuracy` over the positions that are not ignored, both scalars on the
+        device, from one encoder pass.  On a GPU (bf16 encoder rows, up to 16 classes, no dropout) the head, the
+        loss, the accuracy and the gradient with respect to the logits are one HIP launch
+        (:class:`..ops.finetune_head.TokenHeadLossFn`): the logits are never written.  There every negative label
+        is ignored, so ``loss.ignore_index`` must be negative.  ``loss.counter(device)`` gains the batch's live
+        positions, hits and labels ``>= n_classes``; such labels are kept out of the loss on either path."""
+        from ..ops import finetune_head
+        K = self.n_classes
+        cw = loss.weights_on(y.device)
+        if cw is not None and cw.numel() != K:
+            raise ValueError(f"{cw.numel()} class weights for a head of {K} classes")
+        counter = loss.counter(y.device)
+        tokens = x["local"] if isinstance(x, dict) else x
+        # decided before the encoder runs (its fused backend is what yields bf16 rows), so either path encodes once
+        fusable = (finetune_head.LOSS_FUSED and isinstance(self.dropout, nn.Identity) and loss.ignore_index < 0
+                   and y.dtype == torch.int64 and tokens.is_cuda and 1 <= K <= 16
+                   and self.encoder.resolved_backend(tokens.device) == "hip")
+        if fusable:
+            if self.hidden == "all":
+                hs, gs = self._encode_all(x)
+                gin = torch.cat([g.float() for g in gs], dim=-1) if self.global_head is not None else None
+            else:
+                h, g = self._encode(x)
+                hs, gin = [h], (g.float() if self.global_head is not None else None)
+            if finetune_head.supported_loss(hs, K) and y.device == hs[0].device:
+                gterm = None if gin is None else self.global_head(gin)                          # [B, K]
+                return finetune_head.TokenHeadLossFn.apply(*hs, self.head.weight, self.head.bias, gterm, y, cw,
+                                                           loss.label_smoothing, counter)
+            del hs
+        logits = self.forward(x)
+        bad = y >= K
+        yc = torch.where(bad, torch.full_like(y, loss.ignore_index), y)
+        value = loss(logits, yc)
+        with torch.no_grad():
+            valid = yc != loss.ignore_index
+            hits = ((torch.softmax(logits.detach().float(), dim=1).argmax(1) == yc) & valid).sum()
+            n_valid = valid.sum()
+            counter += torch.stack([n_valid, hits, bad.sum()])
+            acc = hits.float() / n_valid.clamp_min(1).float()
+        return value, acc
+
 
 class ProteinBERTForSequenceClassification(_FinetuneBase):
     def __init__(self, encoder: ProteinBERT, n_classes: int = 2, freeze_encoder: bool = True,

@@ -635,6 +635,254 @@ __global__ void __launch_bounds__(256) task_eval_fold_kernel(const float* __rest
   }
 }
 
+// ---- training a per-residue head: the shaped cross-entropy and its logit gradient instead of the logits ----
+//   z[m][k] as above;  p = softmax(z), lp = log p, w = cw (or ones), S = sum_k w_k, c = eps / K
+//   loss_row = (1 - eps) w_y (-lp_y) + c sum_k w_k (-lp_k)          wrow = w_y
+//   g[m][k]  = (1 - eps) w_y (p_k - [k == y]) + c (p_k S - w_k)
+// which is F.cross_entropy(z, y, weight=cw, label_smoothing=eps) before its division by sum wrow: g is written
+// unnormalised and the caller scales the reduced gradients by 1 / sum wrow (pbx_token_head_loss_fold's out[1]).
+// Staging, prefetch and FMA order are token_head_eval_kernel's, statement for statement, so the logits a thread
+// holds are bit for bit token_head_multi_fwd_kernel's and its call (p_k = exp / sum, strict > in ascending k) is
+// token_head_calls_kernel's label.  Row classes as there: y < 0 ignored, y >= K a bad label (counted), both write
+// a zero row of g (the weight-gradient kernels read every row < M) and skip their FMAs.  -lp_k is formed as
+// log(sum) - (z_k - max), so K = 1 gives a loss of exactly +0 and a zero gradient.  Workgroup w writes
+// part[w] = {sum loss_row, sum wrow} (lane-ordered wave reduction, then waves 0..3 in order) and cnt[w] =
+// {live rows, hits, bad labels} (wave ballots: integers); no atomics at all.  The LDS image is the 64 KiB of rows,
+// K * 512 B of weights and ten words.  Rows >= M are neither read nor written; the logits are never written.
+template <int K>
+__global__ void __launch_bounds__(256) token_head_loss_kernel(const MultiSrc src, const int nb,
+                                                              const float* __restrict__ W,
+                                                              const float* __restrict__ b,
+                                                              const float* __restrict__ gterm,
+                                                              const long long* __restrict__ y,
+                                                              const float* __restrict__ cw, const float eps,
+                                                              float* __restrict__ g, float* __restrict__ part,
+                                                              unsigned* __restrict__ cnt, long M, int L) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 256 rows x 256 B
+  __shared__ float ws[K * CH];
+  __shared__ float wsum[4][2];
+  __shared__ unsigned wcnt[4][3];
+  const long m0 = (long)blockIdx.x * 256;
+  const int n = (int)min((long)256, M - m0);
+  const int row = threadIdx.x;
+  const int ldw = nb * CH;
+  // the label is needed only after the block walk: issued first, its latency is behind the first staging
+  const long long yv = row < n ? y[m0 + row] : -1ll;
+  const bool live = yv >= 0 && yv < (long long)K;
+  float acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = b[k];
+  uint4 pre[16];                             // chunk idx = tid + 256 j of block i: row idx >> 4, 16-B chunk idx & 15
+  auto fetch = [&](int i) {
+    const bf16_t* __restrict__ h = src.p[i];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      pre[j] = (idx >> 4) < n ? *reinterpret_cast<const uint4*>(h + (m0 + (idx >> 4)) * CH + (idx & 15) * 8)
+                              : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  auto stage = [&](int i) {                  // the fetched rows (swz256: conflict-free row reads) + W[:, block i]
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int idx = threadIdx.x + j * 256;
+      *reinterpret_cast<uint4*>(smem + swz256(idx >> 4, idx & 15)) = pre[j];
+    }
+    for (int j = threadIdx.x; j < K * CH; j += 256) ws[j] = W[(j >> 7) * ldw + i * CH + (j & (CH - 1))];
+  };
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int i = 0; i < nb; ++i) {
+    if (i + 1 < nb) fetch(i + 1);
+    if (live) {
+#pragma unroll 4
+      for (int c = 0; c < 16; ++c) {
+        float v[8];
+        unpack8(*reinterpret_cast<const uint4*>(smem + swz256(row, c)), v);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float* wr = ws + k * CH + c * 8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[k] = fmaf(v[e], wr[e], acc[k]);
+        }
+      }
+    }
+    if (i + 1 < nb) {
+      __syncthreads();                       // every thread is done with block i's image
+      stage(i + 1);
+      __syncthreads();
+    }
+  }
+  float lrow = 0.f, wrow = 0.f;              // no early return: every thread reaches the barrier below
+  bool hit = false;
+  if (live) {
+    if (gterm != nullptr) {
+      const float* gt = gterm + ((m0 + row) / L) * K;
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] += gt[k];
+    }
+    const int yi = (int)yv;
+    float wk[K];                             // uniform addresses: the class weights stay in scalar registers
+    float S = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      wk[k] = cw != nullptr ? cw[k] : 1.f;
+      S += wk[k];
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, acc[k]);
+    float d[K];                              // z_k - max
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      d[k] = acc[k] - mx;
+      acc[k] = __expf(d[k]);
+      s += acc[k];
+    }
+    const float lse = logf(s);
+    float bv = -1.f, wy = 0.f, nly = 0.f, sm = 0.f;
+    int bi = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {            // k ascending: a strict > keeps the lowest index
+      acc[k] = acc[k] / s;
+      if (acc[k] > bv) {
+        bv = acc[k];
+        bi = k;
+      }
+      const float nl = lse - d[k];           // -lp_k
+      wy = k == yi ? wk[k] : wy;
+      nly = k == yi ? nl : nly;
+      sm = fmaf(wk[k], nl, sm);
+    }
+    const float a = (1.f - eps) * wy, c = eps / (float)K;
+    lrow = a * nly + c * sm;
+    wrow = wy;
+    hit = bi == yi;
+    float* gr = g + (m0 + row) * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) gr[k] = a * (acc[k] - (k == yi ? 1.f : 0.f)) + c * (acc[k] * S - wk[k]);
+  } else if (row < n) {
+    float* gr = g + (m0 + row) * K;
+#pragma unroll
+    for (int k = 0; k < K; ++k) gr[k] = 0.f;
+  }
+  const unsigned nlive = (unsigned)__popcll(__ballot(live));
+  const unsigned nhit = (unsigned)__popcll(__ballot(hit));
+  const unsigned nbad = (unsigned)__popcll(__ballot(yv >= (long long)K));
+  lrow = wave_reduce_sum(lrow);
+  wrow = wave_reduce_sum(wrow);
+  if ((threadIdx.x & 63) == 0) {
+    const int wv = threadIdx.x >> 6;
+    wsum[wv][0] = lrow;
+    wsum[wv][1] = wrow;
+    wcnt[wv][0] = nlive;
+    wcnt[wv][1] = nhit;
+    wcnt[wv][2] = nbad;
+  }
+  __syncthreads();                           // the four waves' sums are complete
+  if (threadIdx.x < 2)
+    part[(size_t)blockIdx.x * 2 + threadIdx.x] =
+        ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+  else if (threadIdx.x >= 64 && threadIdx.x < 67) {
+    const int j = threadIdx.x - 64;
+    cnt[(size_t)blockIdx.x * 3 + j] = wcnt[0][j] + wcnt[1][j] + wcnt[2][j] + wcnt[3][j];
+  }
+}
+
+template <int K>
+int token_head_loss_launch(const MultiSrc& src, int nb, const float* W, const float* b, const float* gterm,
+                           const long long* y, const float* cw, float eps, float* g, float* part, unsigned* cnt,
+                           long M, int L, hipStream_t st) {
+  static bool attr = false;                  // 64 KiB dynamic + the static weight slice exceed the default
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)token_head_loss_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              256 * 256);
+    attr = true;
+  }
+  hipLaunchKernelGGL(token_head_loss_kernel<K>, dim3((unsigned)((M + 255) / 256)), dim3(256), 256 * 256, st, src, nb,
+                     W, b, gterm, y, cw, eps, g, part, cnt, M, L);
+  return pbx_launch_status();
+}
+
+// ---- fold: one batch's partials of token_head_loss_kernel -> the step's loss, gradient scale and accuracy.
+// One block.  The two fp64 sums take task_eval_fold_kernel block (0, 0)'s order: thread t adds the contiguous run
+// t * run .. (t + 1) * run - 1 (run = ceil(nwg / 256)) in ascending order, threads 0..15 add the run sums
+// 16 t .. 16 t + 15, thread 0 adds those 16.  The three counters are integer sums (exact in any order).
+//   out[0] = sum loss / sum w, out[1] = 1 / sum w (nan and 0 when sum w == 0: an all-ignored batch has a nan
+//   loss and a zero gradient, as in torch), out[2] = hits / max(1, live);  acc_cnt [3] int64 += live, hits, bad
+__global__ void __launch_bounds__(256) token_head_loss_fold_kernel(const float* __restrict__ part,
+                                                                   const unsigned* __restrict__ cnt, int nwg,
+                                                                   float* __restrict__ out,
+                                                                   long long* __restrict__ acc_cnt) {
+  __shared__ double dred[2][256];
+  __shared__ double dred2[2][16];
+  __shared__ unsigned long long ured[3][256];
+  const int tid = threadIdx.x;
+  const int run = (nwg + 255) / 256;
+  const int i0 = min(nwg, tid * run), i1 = min(nwg, (tid + 1) * run);
+  double a = 0.0, w = 0.0;
+  unsigned long long c0 = 0ull, c1 = 0ull, c2 = 0ull;
+  int i = i0;
+  for (; i + 3 < i1; i += 4) {               // four partial rows' loads in flight, added in ascending order
+    float p[8];
+    unsigned c[12];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) p[u] = part[2 * (size_t)i + u];
+#pragma unroll
+    for (int u = 0; u < 12; ++u) c[u] = cnt[3 * (size_t)i + u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      a += (double)p[2 * u];
+      w += (double)p[2 * u + 1];
+      c0 += c[3 * u];
+      c1 += c[3 * u + 1];
+      c2 += c[3 * u + 2];
+    }
+  }
+  for (; i < i1; ++i) {
+    a += (double)part[2 * (size_t)i];
+    w += (double)part[2 * (size_t)i + 1];
+    c0 += cnt[3 * (size_t)i];
+    c1 += cnt[3 * (size_t)i + 1];
+    c2 += cnt[3 * (size_t)i + 2];
+  }
+  dred[0][tid] = a;
+  dred[1][tid] = w;
+  ured[0][tid] = c0;
+  ured[1][tid] = c1;
+  ured[2][tid] = c2;
+  __syncthreads();
+  if (tid < 32) {
+    const int q = tid >> 4, t = tid & 15;
+    double s = dred[q][t * 16];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) s += dred[q][t * 16 + j];
+    dred2[q][t] = s;
+  } else if (tid >= 64 && tid < 67) {
+    unsigned long long s = 0ull;
+    for (int j = 0; j < 256; ++j) s += ured[tid - 64][j];
+    ured[tid - 64][0] = s;                   // slot 0 is read by this thread alone before the barrier below
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sl = dred2[0][0], sw = dred2[1][0];
+#pragma unroll
+    for (int t = 1; t < 16; ++t) {
+      sl += dred2[0][t];
+      sw += dred2[1][t];
+    }
+    const unsigned long long live = ured[0][0], hits = ured[1][0], bad = ured[2][0];
+    out[0] = sw == 0.0 ? __builtin_nanf("") : (float)(sl / sw);
+    out[1] = sw == 0.0 ? 0.f : (float)(1.0 / sw);
+    out[2] = (float)((double)hits / (double)(live > 0ull ? live : 1ull));
+    acc_cnt[0] += (long long)live;
+    acc_cnt[1] += (long long)hits;
+    acc_cnt[2] += (long long)bad;
+  }
+}
+
 bool multi_src(const void* const* srcs, int nb, MultiSrc& ms) {
   if (srcs == nullptr || nb < 1 || nb > MAXSRC) return false;
   for (int i = 0; i < MAXSRC; ++i) {
@@ -733,6 +981,47 @@ PBX_EXPORT int pbx_task_eval_fold(const float* loss_part, const unsigned* cnt_pa
   const int rs = nwg >= 16 * 256 ? 16 : (nwg + 255) / 256;     // row ranges of <= 256 partial rows, at most 16 of them
   hipLaunchKernelGGL(task_eval_fold_kernel, dim3(1 + (nc + 15) / 16, rs), dim3(256), 0, st, loss_part, cnt_part, nwg,
                      nc, n_sequences, acc_loss, acc_cnt);
+  return pbx_launch_status();
+}
+
+// Workgroups of pbx_token_head_loss on M rows (workgroup w owns rows 256 w .. 256 w + 255): the partial rows it writes.
+PBX_EXPORT int pbx_token_head_loss_parts(long M) {
+  return M < 1 ? 0 : (int)((M + 255) / 256);
+}
+
+// Training loss of a per-residue head: operands as pbx_token_head_eval plus cw ([K] fp32 class weights, null:
+// all ones) and the label smoothing eps in [0, 1) -> g [M][K] fp32, the unnormalised gradient of the weighted,
+// smoothed cross-entropy sum with respect to the logits (zero rows where y < 0 or y >= K; every row < M is
+// written), part [nwg][2] fp32 (sum of the rows' losses, sum of their weights) and cnt [nwg][3] uint32 (live
+// rows, hits, bad labels), nwg = pbx_token_head_loss_parts(M).  The logits are not written.  No atomics: bitwise
+// repeatable.
+PBX_EXPORT int pbx_token_head_loss(const void* const* srcs, int nb, const float* W, const float* b,
+                                   const float* gterm, const long long* y, const float* cw, float eps, float* g,
+                                   float* part, unsigned* cnt, long M, int K, int L, hipStream_t st) {
+  MultiSrc ms;
+  if (M < 1 || L < 1 || W == nullptr || b == nullptr || y == nullptr || g == nullptr || part == nullptr ||
+      cnt == nullptr || !(eps >= 0.f && eps < 1.f) || !multi_src(srcs, nb, ms))
+    return (int)hipErrorInvalidValue;
+#define PBX_LOSS_CASE(KK) \
+  case KK: return token_head_loss_launch<KK>(ms, nb, W, b, gterm, y, cw, eps, g, part, cnt, M, L, st);
+  switch (K) {
+    PBX_LOSS_CASE(1) PBX_LOSS_CASE(2) PBX_LOSS_CASE(3) PBX_LOSS_CASE(4)
+    PBX_LOSS_CASE(5) PBX_LOSS_CASE(6) PBX_LOSS_CASE(7) PBX_LOSS_CASE(8)
+    PBX_LOSS_CASE(9) PBX_LOSS_CASE(10) PBX_LOSS_CASE(11) PBX_LOSS_CASE(12)
+    PBX_LOSS_CASE(13) PBX_LOSS_CASE(14) PBX_LOSS_CASE(15) PBX_LOSS_CASE(16)
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef PBX_LOSS_CASE
+}
+
+// One batch's partials of pbx_token_head_loss -> out [3] fp32 (mean loss = sum loss / sum w, 1 / sum w, accuracy
+// = hits / max(1, live); nan and 0 for the first two when sum w == 0) and acc_cnt [3] int64 += (live, hits, bad);
+// one launch, fp64 sums in a fixed order.
+PBX_EXPORT int pbx_token_head_loss_fold(const float* part, const unsigned* cnt, int nwg, float* out,
+                                        long long* acc_cnt, hipStream_t st) {
+  if (part == nullptr || cnt == nullptr || out == nullptr || acc_cnt == nullptr || nwg < 1)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(token_head_loss_fold_kernel, dim3(1), dim3(256), 0, st, part, cnt, nwg, out, acc_cnt);
   return pbx_launch_status();
 }
 

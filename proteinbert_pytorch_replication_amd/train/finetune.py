@@ -10,7 +10,10 @@ epoch, metrics called as ``metric(softmax(logits, dim=1), y)`` - with these MI35
 * ``X`` may be a tensor or the pretraining-style dict; ``(X, y)`` batches go to ``device`` with
   ``non_blocking`` copies;
 * under data parallelism (``ddp`` given) gradients are all-reduced through the bucketed RCCL
-  reducer before the optimizer step and the epoch means are averaged over ranks.
+  reducer before the optimizer step and the epoch means are averaged over ranks;
+* a :class:`.task_loss.ResidueTaskLoss` (class weights, label smoothing) on a model with a ``loss`` method is
+  taken through ``model.loss(X, y, loss_fn)``: on a GPU one HIP launch computes the head, the loss, the
+  accuracy and the logit gradient, and the logits never reach memory (:func:`_fused_loss_step`).
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import torch.nn.functional as F
 
 from ..parallel import dist as pdist
 from .optim import FusedAdam
+from .task_loss import N_BAD, ResidueTaskLoss
 
 
 def _to(x, device):
@@ -49,10 +53,16 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
     n = 0
     fused = isinstance(optimizer, FusedAdam)
     params = [p for p in model.parameters() if p.requires_grad]
+    by_model = _fused_loss_step(model, loss_fn, metrics)
+    if by_model:
+        loss_fn.counter(device).zero_()
     for X, y in dataloader:
         X, y = _to(X, device), _to(y, device)
-        logits = model(X)
-        loss = loss_fn(logits, y)
+        if by_model:
+            loss, acc = model.loss(X, y, loss_fn)
+        else:
+            logits = model(X)
+            loss = loss_fn(logits, y)
         loss_sum += loss.detach().float()
         optimizer.zero_grad()
         loss.backward()
@@ -64,13 +74,25 @@ def train_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, opt
             else:
                 torch.nn.utils.clip_grad_norm_(params, gradient_clipping_thresh)
         optimizer.step()
-        if metrics:
+        if by_model:
+            for k in metrics:
+                met_sum[k] += acc.detach().float()
+        elif metrics:
             with torch.no_grad():
                 preds = torch.softmax(logits.detach().float(), dim=1)
                 for k, m in metrics.items():
                     met_sum[k] += _metric_value(m(preds, y)).to(device)
         n += 1
-    return _finish(loss_sum, met_sum, n, ddp is not None)
+    return _finish(loss_sum, met_sum, n, ddp is not None, loss_fn.counter(device) if by_model else None)
+
+
+def _fused_loss_step(model, loss_fn, metrics) -> bool:
+    """Whether :func:`train_step` takes ``model.loss(X, y, loss_fn)``: a :class:`.task_loss.ResidueTaskLoss`, a
+    model that has ``loss``, and no metric other than :func:`token_accuracy` closures of the loss's own
+    ``ignore_index`` (``model.loss`` returns that accuracy).  Anything else runs the loop on the logits."""
+    return (isinstance(loss_fn, ResidueTaskLoss) and callable(getattr(model, "loss", None))
+            and all(getattr(m, "token_accuracy_ignore_index", None) == loss_fn.ignore_index
+                    for m in metrics.values()))
 
 
 def test_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, metrics: Dict[str, Callable],
@@ -97,11 +119,19 @@ def test_step(model: torch.nn.Module, dataloader, loss_fn: torch.nn.Module, metr
     return _finish(loss_sum, met_sum, n, distributed)
 
 
-def _finish(loss_sum, met_sum, n, distributed) -> Tuple[float, Dict[str, float]]:
+def _finish(loss_sum, met_sum, n, distributed, counter=None) -> Tuple[float, Dict[str, float]]:
+    """The epoch's one host read.  ``counter`` (``ResidueTaskLoss.counter``) travels in the same copy; labels
+    it counted as ``>= n_classes`` are an error."""
     vals = torch.stack([loss_sum] + [met_sum[k] for k in met_sum]) / max(1, n)
     if distributed:
         pdist.all_reduce_mean_(vals)
-    vals = vals.cpu().tolist()
+    if counter is not None:
+        host = torch.cat([vals.double(), counter[N_BAD:N_BAD + 1].double()]).cpu().tolist()
+        vals, bad = host[:-1], int(host[-1])
+        if bad:
+            raise ValueError(f"{bad} training labels are outside the head's classes; labels below 0 are ignored")
+    else:
+        vals = vals.cpu().tolist()
     return vals[0], {k: v for k, v in zip(met_sum, vals[1:])}
 
 
@@ -112,6 +142,7 @@ def token_accuracy(ignore_index: int = -100) -> Callable:
         valid = y != ignore_index
         hit = (preds.argmax(1) == y) & valid
         return hit.sum().float() / valid.sum().clamp_min(1).float()
+    _acc.token_accuracy_ignore_index = ignore_index      # train_step recognises the closure by this tag
     return _acc
 
 
