@@ -11,7 +11,8 @@ from .config import (ModelConfig, DataConfig, OptimConfig, DistConfig, KernelCon
                      RunConfig, PRESETS, get_preset, apply_overrides, load_yaml)
 from .models import ProteinBERT, ProteinBERTBlock, GlobalAttention, build_model
 from .inference import Predictor
+from .search import EmbeddingIndex
 
 __all__ = ["ModelConfig", "DataConfig", "OptimConfig", "DistConfig", "KernelConfig", "TrainConfig",
            "RunConfig", "PRESETS", "get_preset", "apply_overrides", "load_yaml", "ProteinBERT",
-           "ProteinBERTBlock", "GlobalAttention", "build_model", "Predictor", "__version__"]
+           "ProteinBERTBlock", "GlobalAttention", "build_model", "Predictor", "EmbeddingIndex", "__version__"]

@@ -8,6 +8,8 @@ COMMANDS = {
     "finetune": ("train", "finetune_main"),
     "predict": ("predict", "main"),
     "evaluate": ("evaluate", "main"),
+    "index": ("search", "index_main"),
+    "search": ("search", "search_main"),
     "dummy-tests": ("dummy_tests", "main"),
 }
 
