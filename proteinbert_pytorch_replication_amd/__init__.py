@@ -10,9 +10,9 @@ __version__ = "0.1.0"
 from .config import (ModelConfig, DataConfig, OptimConfig, DistConfig, KernelConfig, TrainConfig,
                      RunConfig, PRESETS, get_preset, apply_overrides, load_yaml)
 from .models import ProteinBERT, ProteinBERTBlock, GlobalAttention, build_model
-from .inference import Predictor
+from .inference import Predictor, parse_variant
 from .search import EmbeddingIndex
 
 __all__ = ["ModelConfig", "DataConfig", "OptimConfig", "DistConfig", "KernelConfig", "TrainConfig",
            "RunConfig", "PRESETS", "get_preset", "apply_overrides", "load_yaml", "ProteinBERT",
-           "ProteinBERTBlock", "GlobalAttention", "build_model", "Predictor", "EmbeddingIndex", "__version__"]
+           "ProteinBERTBlock", "GlobalAttention", "build_model", "Predictor", "parse_variant", "EmbeddingIndex", "__version__"]

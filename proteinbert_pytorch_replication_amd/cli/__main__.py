@@ -7,6 +7,7 @@ COMMANDS = {
     "pretrain": ("train", "pretrain_main"),
     "finetune": ("train", "finetune_main"),
     "predict": ("predict", "main"),
+    "score": ("score", "main"),
     "evaluate": ("evaluate", "main"),
     "index": ("search", "index_main"),
     "search": ("search", "search_main"),

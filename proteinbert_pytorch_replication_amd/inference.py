@@ -17,6 +17,14 @@ token tensors), any subset of
 ``hidden_states``    ``hidden_global`` ``[N, blocks, G]`` / ``hidden_pooled``    fp32
                      ``[N, blocks, 128]``: ``global`` / ``pooled`` after every
                      block
+``residue_llr``      ``residue_llr`` ``[N, L, V]``: log-odds of substituting     fp32
+                     every token at every position
+``residue_logp``     ``residue_logp`` ``[N, L]``: log-probability of the         fp32
+                     residue that is there
+``residue_entropy``  ``residue_entropy`` ``[N, L]``: entropy over the            fp32
+                     vocabulary, in nats
+``pll``              ``pll`` ``[N]``: pseudo-log-likelihood; ``n_residues``      fp32 / int32
+                     ``[N]``: the positions it sums over
 ``task:NAME``        ``task_NAME_labels`` / ``task_NAME_label_probs``:           int32 / fp32
                      ``[N, L]`` (residue head) or ``[N]`` (per-protein
                      classifier); a regression head (``n_classes == 1``) gives
@@ -53,6 +61,23 @@ runs, or use a ``semantics="paper"`` model (softmax over the vocabulary), whose 
 Embeddings and GO predictions do not depend on the batch in either semantics.  Neither do the ``task:`` /
 ``task_probs:`` outputs: a task head's softmax runs over its classes, per residue or per protein, so they are
 per sequence whatever the model's semantics (the encoder itself never mixes sequences).
+
+**Scores: variant effects and pseudo-log-likelihood.**  ProteinBERT is a denoising model without a mask token,
+so a sequence is scored by the wild-type marginal: one encoder pass over the unmodified sequence, then
+arithmetic on the local head's logits ``z[p, v]``.  With ``x`` the token at a position and the position *live*
+when ``UNK_ID <= x < V`` (the task heads' rule: not ``<pad>``, ``<sos>``, ``<eos>``; an id outside the
+vocabulary is not live either): ``residue_llr[p, a] = z[a] - z[x]`` (a difference of logits, the column of
+``x`` exactly ``+0.0``), ``residue_logp[p] = log softmax_v(z)[x]``, ``residue_entropy[p]`` the entropy of
+``softmax_v(z)`` in nats; zeros where the position is not live.  ``pll`` is the sum of ``residue_logp`` over the
+``n_residues`` live positions (fp64 accumulation in a fixed order, rounded once; 0 for a sequence without one);
+the pseudo-perplexity ``exp(-pll / n_residues)`` is left to the caller and is ``nan`` for such a sequence.  On
+the HIP backend these are ``pbx_lhead_scores`` + ``pbx_seq_score_fold`` (:func:`.ops.infer_heads.local_scores`;
+the ``[N, L, V]`` matrix is written only when ``residue_llr`` is requested), on the PyTorch backend
+:func:`.ops.infer_heads.local_scores_torch`.  They are computed from the logits, which are per row in both
+semantics, so they do not depend on batch mates.  For a paper-semantics model ``residue_logp`` is the log of
+the model's own ``residue_probs`` at the wild-type token.  For a reference-semantics model these quantities are
+functions of the logits under a vocabulary softmax: that is NOT the batch-axis quantity the model was trained
+on.  :meth:`Predictor.score_variants` and :meth:`Predictor.mutation_scan` are built on these outputs.
 """
 from __future__ import annotations
 
@@ -63,11 +88,14 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from .data.transforms import SimpleCharacterTokenizer, pad_to
-from .data.vocab import PAD_ID, create_amino_acid_vocab
+from .data.vocab import ALL_AMINO_ACIDS, PAD_ID, SPECIAL_TOKENS, create_amino_acid_vocab
 from .models.finetune import (ProteinBERTForSequenceClassification, ProteinBERTForTokenClassification,
                               load_finetuned_head)
 
-OUTPUTS = ("global", "pooled", "residue", "go_probs", "go_topk", "residue_probs", "residue_tokens", "hidden_states")
+OUTPUTS = ("global", "pooled", "residue", "go_probs", "go_topk", "residue_probs", "residue_tokens", "hidden_states",
+           "residue_llr", "residue_logp", "residue_entropy", "pll")
+SCORE_OUTPUTS = ("residue_llr", "residue_logp", "residue_entropy", "pll")
+SCORE_STRATEGIES = ("wt_marginal", "pll_ratio")
 DEFAULT_OUTPUTS = ("global", "pooled", "go_topk")
 
 
@@ -105,6 +133,40 @@ def _check_outputs(outputs: Iterable[str], heads: Optional[dict] = None) -> tupl
 
 def _is_regression(head) -> bool:
     return isinstance(head, ProteinBERTForSequenceClassification) and head.n_classes == 1
+
+
+_SUBSTITUTION = re.compile(r"([A-Za-z])([0-9]+)([A-Za-z])\Z")
+_AA_IDS = {c: len(SPECIAL_TOKENS) + i for i, c in enumerate(ALL_AMINO_ACIDS)}
+
+
+def parse_variant(variant: str, sequence: str) -> List[Tuple[int, int]]:
+    """``[(token position, new token id), ...]`` of a variant of ``sequence`` (the residues the model sees, so
+    at most ``L - 2`` of them): one or more substitutions joined by ``:``, each ``<wild-type letter><1-based
+    position><new letter>``, e.g. ``"A123G"`` or ``"A123G:L45P"``.  Residue ``i`` sits at token position ``i``
+    (``<sos>`` is position 0).  ``ValueError`` naming the variant for bad syntax, a letter outside the
+    vocabulary, a position outside the sequence, a wild-type letter that is not the sequence's, or a position
+    given twice."""
+    if not isinstance(variant, str) or not variant:
+        raise ValueError(f"variant {variant!r}: expected substitutions such as 'A123G' joined by ':'")
+    subs: List[Tuple[int, int]] = []
+    for part in variant.split(":"):
+        m = _SUBSTITUTION.match(part)
+        if m is None:
+            raise ValueError(f"variant {variant!r}: {part!r} is not <letter><position><letter>, e.g. 'A123G'")
+        wt, pos, new = m.group(1), int(m.group(2)), m.group(3)
+        for c in (wt, new):
+            if c not in _AA_IDS:
+                raise ValueError(f"variant {variant!r}: letter {c!r} is outside the vocabulary {ALL_AMINO_ACIDS}")
+        if not 1 <= pos <= len(sequence):
+            raise ValueError(f"variant {variant!r}: position {pos} is outside the sequence's {len(sequence)} "
+                             f"scored residues")
+        if sequence[pos - 1] != wt:
+            raise ValueError(f"variant {variant!r}: the sequence has {sequence[pos - 1]!r} at position {pos}, "
+                             f"not {wt!r}")
+        if any(p == pos for p, _ in subs):
+            raise ValueError(f"variant {variant!r}: position {pos} is given twice")
+        subs.append((pos, _AA_IDS[new]))
+    return subs
 
 
 def _calls_torch(p: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -257,6 +319,23 @@ class Predictor:
             if "task_probs" in kinds:
                 out[f"task_{name}_probs"] = p
 
+    def _score_outputs(self, out, outputs, fn, h, tokens) -> None:
+        """The requested ``SCORE_OUTPUTS`` of this batch's encoder pass through ``fn``
+        (:func:`.ops.infer_heads.local_scores` or its torch definition); ``llr`` is stored only when
+        ``residue_llr`` is requested."""
+        if not any(o in outputs for o in SCORE_OUTPUTS):
+            return
+        lo = self.model.pretraining_local_output[0]
+        llr, logp, ent, pll, n_live = fn(h, lo.weight, lo.bias, tokens, store_llr="residue_llr" in outputs)
+        if "residue_llr" in outputs:
+            out["residue_llr"] = llr
+        if "residue_logp" in outputs:
+            out["residue_logp"] = logp
+        if "residue_entropy" in outputs:
+            out["residue_entropy"] = ent
+        if "pll" in outputs:
+            out["pll"], out["n_residues"] = pll, n_live
+
     def _predict_hip(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
         from .ops import infer_heads as ih
         from .ops.fused_model import fused_encode
@@ -306,6 +385,7 @@ class Predictor:
         if want_hidden:
             out["hidden_global"] = torch.stack(hidden_g, dim=1)
             out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
+        self._score_outputs(out, outputs, ih.local_scores, h, tokens)
         self._task_outputs(out, req, tokens, h, g, hs_all, gs_all, hip=True)
         return out
 
@@ -352,6 +432,8 @@ class Predictor:
         if want_hidden:
             out["hidden_global"] = torch.stack(hidden_g, dim=1)
             out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
+        from .ops.infer_heads import local_scores_torch
+        self._score_outputs(out, outputs, local_scores_torch, h, tokens)
         self._task_outputs(out, req, tokens, h, g, hs_all, gs_all, hip=False)
         return out
 
@@ -383,3 +465,64 @@ class Predictor:
         if cuda:
             torch.cuda.synchronize(self.device)
         return host
+
+    # ------------------------------------------------------------------------
+    def _wild_type(self, wild_type: str, truncate: bool) -> Tuple[torch.Tensor, str]:
+        """``(tokens [1, L], the residues that are scored)`` of one sequence."""
+        if not isinstance(wild_type, str):
+            raise TypeError(f"expected a sequence string, got {type(wild_type).__name__}")
+        tokens = self.tokenize([wild_type], truncate)
+        return tokens, wild_type[:self.model.sequences_length - 2]
+
+    def score_variants(self, wild_type: str, variants: Sequence[str], strategy: str = "wt_marginal",
+                       truncate: bool = False) -> dict:
+        """Scores of substitution variants of ``wild_type`` (``"A123G"``, ``"A123G:L45P"``: see
+        :func:`parse_variant`; any malformed one raises ``ValueError`` naming it, before the encoder runs).
+
+        ``strategy="wt_marginal"``: one encoder pass over the wild type; a variant's score is the sum of
+        ``residue_llr[pos, new]`` over its substitutions, gathered on the device and read once.
+        ``strategy="pll_ratio"``: every variant goes through the encoder (batches of ``batch_size``, only the
+        ``pll`` output, so no ``llr`` is stored) and its score is ``pll(variant) - pll(wild type)``.
+
+        Returns ``{"scores": fp32 [n], "variants": list, "strategy": str, "wild_type_pll": float}``."""
+        if strategy not in SCORE_STRATEGIES:
+            raise ValueError(f"strategy {strategy!r}: expected one of {SCORE_STRATEGIES}")
+        variants = list(variants)
+        tokens, seq = self._wild_type(wild_type, truncate)
+        subs = [parse_variant(v, seq) for v in variants]
+        n = len(variants)
+        width = max([len(s) for s in subs], default=1)
+        # [n, width] index matrices, short variants padded with (position 0, token 0) under a zero mask
+        pos = torch.zeros((n, width), dtype=torch.long)
+        new = torch.zeros((n, width), dtype=torch.long)
+        mask = torch.zeros((n, width), dtype=torch.float32)
+        for i, s in enumerate(subs):
+            for j, (p, a) in enumerate(s):
+                pos[i, j], new[i, j], mask[i, j] = p, a, 1.0
+        if strategy == "wt_marginal":
+            out = self.predict_batch(tokens, outputs=("residue_llr", "pll"))
+            dev = out["residue_llr"].device
+            picked = out["residue_llr"][0][pos.to(dev), new.to(dev)] * mask.to(dev)        # [n, width]
+            both = torch.cat([picked.sum(dim=1), out["pll"]]).cpu()                        # the one host read
+            scores, wt_pll = both[:n].clone(), float(both[n])
+        else:
+            rows = tokens.repeat(n + 1, 1)                       # row 0 stays the wild type
+            live = mask.bool()
+            rows[1:][torch.arange(n).unsqueeze(1).expand(n, width)[live], pos[live]] = new[live]
+            pll = self.predict(rows, outputs=("pll",))["pll"]
+            scores, wt_pll = pll[1:] - pll[0], float(pll[0])
+        return {"scores": scores, "variants": variants, "strategy": strategy, "wild_type_pll": wt_pll}
+
+    def mutation_scan(self, sequence: str, truncate: bool = False) -> dict:
+        """The deep mutational scan of one sequence from a single encoder pass: ``llr [n_res, 22]`` (the
+        log-odds of every substitution at every residue position, without ``<sos>`` / ``<eos>``; columns in
+        the order of ``letters`` = ``data.vocab.ALL_AMINO_ACIDS``), ``logp [n_res]``, ``entropy [n_res]``,
+        ``pll`` (float) and ``letters``, as CPU tensors."""
+        tokens, seq = self._wild_type(sequence, truncate)
+        out = self.predict_batch(tokens, outputs=("residue_llr", "residue_logp", "residue_entropy", "pll"))
+        n_res = len(seq)
+        cols = torch.tensor(self.tokenizer.vocab.lookup_indices(ALL_AMINO_ACIDS), device=out["pll"].device)
+        rows = slice(1, 1 + n_res)                               # position 0 is <sos>
+        return {"llr": out["residue_llr"][0, rows].index_select(-1, cols).cpu(),
+                "logp": out["residue_logp"][0, rows].cpu(), "entropy": out["residue_entropy"][0, rows].cpu(),
+                "pll": float(out["pll"][0]), "letters": ALL_AMINO_ACIDS}

@@ -1,4 +1,4 @@
-"""Prediction heads for inference (``csrc/infer.hip``, ``EPI_GO_PROB`` in ``csrc/gemm.hip``).
+"""Prediction heads for inference (``csrc/infer.hip``, ``csrc/score.hip``, ``EPI_GO_PROB`` in ``csrc/gemm.hip``).
 
 The training heads produce a loss and gradients, the evaluation heads (:mod:`.eval_heads`) loss partials and
 counts; neither returns a prediction.  Here each head writes what :mod:`..inference` hands to the caller:
@@ -12,7 +12,11 @@ counts; neither returns a prediction.  Here each head writes what :mod:`..infere
 * :func:`masked_mean_pool` -- the mean of ``h`` over the non-``<pad>`` positions;
 * :func:`token_head_calls` -- a fine-tuned per-residue task head (``csrc/finetune.hip``): the class of every
   residue, its probability and optionally the class probabilities, from 1..8 row sources in one launch whose
-  logits stay in registers.
+  logits stay in registers;
+* :func:`local_scores` -- variant-effect and likelihood scores from the local head's logits
+  (``csrc/score.hip``): per-position log-odds of every substitution, the log-probability of the residue that
+  is there and the entropy, and the per-sequence pseudo-log-likelihood, identical in both semantics
+  (:func:`local_scores_torch` is the same definition on any device).
 
 No autograd Function is involved, nothing is kept for a backward pass, and every output is bitwise repeatable.
 """
@@ -30,6 +34,7 @@ from .global_track import bf16_of
 F32 = torch.float32
 TOPK_MAX_K = 64                 # pbx_row_topk: results live one per lane of a wave
 TOPK_MAX_COLS = 256 * 64        # ... and the row in registers, at most 256 values per lane
+SCORE_MAX_V = 32                # pbx_lhead_scores: the padded vocabulary of one MFMA tile
 
 
 def _s(dev) -> int:
@@ -217,6 +222,88 @@ def token_head_calls_torch(hs: Sequence[torch.Tensor], weight: torch.Tensor, bia
     if P is not None:
         P.copy_(probs)
     return P, labels, pmax
+
+
+def _score_args(h: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, tokens: torch.Tensor,
+                store_llr: bool, out: Optional[torch.Tensor]) -> Tuple[int, int, int]:
+    """``(B, L, V)`` of a :func:`local_scores` call, or ``ValueError``: shapes and dtypes only, so it holds on
+    any device."""
+    if h.dim() != 3 or h.shape[0] < 1 or h.shape[1] < 1:
+        raise ValueError(f"local_scores: h {tuple(h.shape)}: expected a non-empty [B, L, C] tensor")
+    B, L, C = h.shape
+    V = weight.shape[0] if weight.dim() == 2 else 0
+    if not 1 <= V <= SCORE_MAX_V or weight.shape[1] != C:
+        raise ValueError(f"local_scores: weight {tuple(weight.shape)}: expected [V, {C}], 1 <= V <= {SCORE_MAX_V}")
+    if tuple(bias.shape) != (V,):
+        raise ValueError(f"local_scores: bias {tuple(bias.shape)}: expected {(V,)}")
+    if tuple(tokens.shape) != (B, L) or tokens.dtype != torch.int64:
+        raise ValueError(f"local_scores: tokens must be int64 {(B, L)}")
+    if out is not None and not store_llr:
+        raise ValueError("local_scores: out= is where llr is stored: pass store_llr=True")
+    if out is not None:
+        _probs_out(out, True, B, L, V, None)        # its shape, dtype and layout
+        if out.device != h.device:
+            raise ValueError("local_scores: out must be on h's device")
+    return B, L, V
+
+
+def local_scores(h: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, tokens: torch.Tensor,
+                 store_llr: bool = False, out: Optional[torch.Tensor] = None):
+    """Scores from the local head's logits ``z = h bf16(W)^T + b`` (``pbx_lhead_scores`` and
+    ``pbx_seq_score_fold``, ``csrc/score.hip``; the operands and accumulation of :func:`local_probs_paper`), the
+    same in both semantics: ``h [B, L, 128]`` bf16, ``weight [V, 128]``, ``bias [V]``, ``V <= 32``, ``tokens
+    [B, L]`` int64.  Returns ``(llr [B, L, V] fp32 or None, logp [B, L], entropy [B, L], pll [B] fp32, n_live
+    [B] int32)``.  At a live position (``UNK_ID <= token < V``: not ``<pad>``, ``<sos>``, ``<eos>``, nor an id
+    outside the vocabulary, which indexes nothing) ``llr[a] = z[a] - z[token]`` (the token's own column is
+    ``+0.0``), ``logp = log softmax_v(z)[token]`` and ``entropy`` that of ``softmax_v(z)`` in nats; elsewhere
+    zeros.  ``pll`` is the sum of the stored ``logp`` over the ``n_live`` live positions, accumulated in fp64
+    in an order fixed by ``L`` and rounded once.  Every row's outputs depend on that row alone.  ``llr`` is
+    written only with ``store_llr`` (``out``: a contiguous fp32 ``[B, L, V]`` tensor to write it into); without
+    it the launch writes 8 bytes per row.  Everything is validated before the launch."""
+    B, L, V = _score_args(h, weight, bias, tokens, store_llr, out)
+    if not (h.is_cuda and h.dtype == torch.bfloat16 and h.shape[2] == 128):
+        raise ValueError("local_scores: h must be a CUDA bf16 [B, L, 128] tensor "
+                         "(local_scores_torch is the definition on any device)")
+    if tokens.device != h.device:
+        raise ValueError("local_scores: tokens must be on h's device")
+    dev = h.device
+    llr = _probs_out(out, store_llr, B, L, V, dev)
+    hx = h.contiguous()
+    tk = tokens.contiguous()
+    logp = torch.empty((B, L), dtype=F32, device=dev)
+    ent = torch.empty((B, L), dtype=F32, device=dev)
+    pll = torch.empty((B,), dtype=F32, device=dev)
+    n_live = torch.empty((B,), dtype=torch.int32, device=dev)
+    st = _s(dev)
+    _lib.call("pbx_lhead_scores", hx.data_ptr(), weight.detach().float().contiguous().data_ptr(),
+              bias.detach().float().contiguous().data_ptr(), tk.data_ptr(), _lib.ptr(llr), logp.data_ptr(),
+              ent.data_ptr(), int(store_llr), B * L, V, st)
+    _lib.call("pbx_seq_score_fold", logp.data_ptr(), tk.data_ptr(), pll.data_ptr(), n_live.data_ptr(), B, L, V, st)
+    return llr, logp, ent, pll, n_live
+
+
+def local_scores_torch(h: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, tokens: torch.Tensor,
+                       store_llr: bool = False, out: Optional[torch.Tensor] = None):
+    """:func:`local_scores` by definition, on any device and for any channel count, in fp32: ``z =
+    Linear(h.float())``, ``llr`` as a difference of logits, ``logp`` and ``entropy`` from ``log_softmax`` over
+    the vocabulary, ``pll`` as the fp64 sum of the fp32 ``logp`` rounded once.  Each row is computed from that
+    row alone, so a sequence's outputs do not change with its batch mates."""
+    B, L, V = _score_args(h, weight, bias, tokens, store_llr, out)
+    llr = _probs_out(out, store_llr, B, L, V, h.device)
+    tokens = tokens.to(h.device)
+    z = torch.nn.functional.linear(h.float(), weight.detach().float(), bias.detach().float())      # [B, L, V]
+    live = (tokens >= UNK_ID) & (tokens < V)
+    x = torch.where(live, tokens, torch.zeros_like(tokens)).unsqueeze(-1)       # a safe index where not live
+    lq = torch.log_softmax(z, dim=-1)
+    zero = torch.zeros((), dtype=F32, device=h.device)
+    logp = torch.where(live, lq.gather(-1, x).squeeze(-1), zero)
+    ent = torch.where(live, -(lq.exp() * lq).sum(-1), zero)
+    if llr is not None:
+        d = z - z.gather(-1, x)
+        d.scatter_(-1, x, 0.0)                                                  # the token's own column: +0.0
+        llr.copy_(torch.where(live.unsqueeze(-1), d, zero))
+    pll = logp.to(torch.float64).sum(dim=1).to(F32)
+    return llr, logp, ent, pll, live.sum(dim=1).to(torch.int32)
 
 
 def masked_mean_pool(h: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
