@@ -1,13 +1,16 @@
 """``predict``: embeddings, GO-term predictions and residue calls for the records of a FASTA file.
 
     python -m proteinbert_pytorch_replication_amd.cli predict --model model.pt --fasta in.fasta --out out.npz \\
-        [--outputs global,pooled,go_topk] [--go-top-k K] [--batch-size N] [--truncate] \\
+        [--outputs global,pooled,go_topk] [--go-top-k K] [--attention-top-k K] [--batch-size N] [--truncate] \\
         [--head NAME=head.pt ...] [--head-classes NAME=ALPHABET ...]
 
 The model is a file written by ``train.checkpoint.save_final_model`` (or a training checkpoint holding the
 model's config); the ``.npz`` holds ``ids`` (the FASTA record names, in file order) and the arrays of the
 requested outputs (:mod:`..inference`).  bf16 arrays are stored as fp32.  For a reference-semantics model
-the residue probabilities and calls depend on ``--batch-size`` (see :mod:`..inference`).
+the residue probabilities and calls depend on ``--batch-size`` (see :mod:`..inference`).  ``--outputs
+attention,attention_top`` (paper-semantics models only) stores the attention maps ``attention [N, blocks, H, L]``
+and the ``--attention-top-k`` most attended positions per block and head (``attention_top_values`` /
+``attention_top_indices``).
 
 ``--head NAME=PATH`` (repeatable) registers a head file of ``cli finetune`` and adds its ``task:NAME`` output:
 ``task_NAME_labels`` / ``task_NAME_label_probs`` (``task_NAME_values`` for a regression head), and
@@ -52,6 +55,8 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--outputs", default=",".join(DEFAULT_OUTPUTS),
                     help=f"comma-separated subset of {','.join(OUTPUTS)}")
     ap.add_argument("--go-top-k", type=int, default=10)
+    ap.add_argument("--attention-top-k", type=int, default=10,
+                    help="positions per block and head of the attention_top output")
     ap.add_argument("--batch-size", type=int, default=256)
     ap.add_argument("--truncate", action="store_true", help="keep the first L - 2 residues of longer sequences")
     ap.add_argument("--device", default=None, help="default: cuda:0 when there is a GPU, else cpu")
@@ -88,7 +93,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         if name in alphabets and len(alphabets[name]) != head.n_classes:
             raise SystemExit(f"head {name!r}: alphabet {alphabets[name]!r} has {len(alphabets[name])} letters, "
                              f"the head {head.n_classes} classes")
-    res = pred.predict(seqs, outputs=outputs, go_top_k=a.go_top_k, truncate=a.truncate)
+    res = pred.predict(seqs, outputs=outputs, go_top_k=a.go_top_k, truncate=a.truncate,
+                       attention_top_k=a.attention_top_k)
     arrays = {k: (v.float() if v.dtype == torch.bfloat16 else v).numpy() for k, v in res.items()}
     L = model.sequences_length
     for name, alphabet in alphabets.items():

@@ -25,6 +25,12 @@ token tensors), any subset of
                      vocabulary, in nats
 ``pll``              ``pll`` ``[N]``: pseudo-log-likelihood; ``n_residues``      fp32 / int32
                      ``[N]``: the positions it sums over
+``attention``        ``attention`` ``[N, blocks, H, L]``: the weights of the     fp32
+                     global attention, per block and head (paper semantics
+                     only)
+``attention_top``    ``attention_top_values`` / ``attention_top_indices``        fp32 / int32
+                     ``[N, blocks, H, k]``: the ``k`` most attended positions
+                     per block and head (paper semantics only)
 ``task:NAME``        ``task_NAME_labels`` / ``task_NAME_label_probs``:           int32 / fp32
                      ``[N, L]`` (residue head) or ``[N]`` (per-protein
                      classifier); a regression head (``n_classes == 1``) gives
@@ -78,6 +84,26 @@ semantics, so they do not depend on batch mates.  For a paper-semantics model ``
 the model's own ``residue_probs`` at the wild-type token.  For a reference-semantics model these quantities are
 functions of the logits under a vocabulary softmax: that is NOT the batch-axis quantity the model was trained
 on.  :meth:`Predictor.score_variants` and :meth:`Predictor.mutation_scan` are built on these outputs.
+
+**Attention maps: where the model looks.**  The global attention of a ``semantics="paper"`` model (one query per
+head from the global track, a softmax over the positions of the local track) is the interpretable part of the
+architecture.  For block ``i`` with its local output ``h2_i``, the global vector ``g_in_i`` that enters it (the
+input layer's output for block 0, else the previous block's ``g``) and ``mask = tokens != <pad>``:
+``qs = tanh(g_in Wq[h]) / sqrt(K)``, ``s[l] = sum_k qs[k] tanh(h2[l] . Wk[h][:, k])`` and ``attention[n, i, h, :]``
+the softmax of ``s`` over the positions with ``mask``: exactly 0.0 at ``<pad>``, all zeros for a sequence of
+``<pad>`` only, and ``<sos>`` / ``<eos>`` are positions the model attends to (not masked).  These are the
+operands the encoder's own attention used.  ``attention_top`` gives the ``k = attention_top_k`` largest weights of
+every (block, head) row, descending, equal weights by ascending position (a stable sort); where a row has fewer
+than ``k`` live positions the remaining entries are what that order gives for its zeros: value 0.0, the masked
+positions in ascending order.  ``attention_top_k > L`` raises.  Both share the batch's single encoder pass with
+every other output (the per-block states come from the encoder's taps); with neither requested no tap is
+installed and none of this runs.  On the HIP backend they are ``pbx_attn_map_scores`` +
+``pbx_attn_map_normalize`` (:func:`.ops.attention_maps.attention_maps`; ``key_dim = 64``, ``local_dim = 128``, at
+most 8 heads, 8 blocks per launch pair) and ``pbx_row_topk``; elsewhere
+:func:`.ops.attention_maps.attention_maps_torch`.  A **reference-semantics** model raises ``ValueError``: its
+softmax runs over K identical query rows, so every weight is ``1/K`` by construction, ``Wq`` / ``Wk`` never
+influence the model (they are non-persistent random buffers and the model computes the closed form), and a
+constant would be returned as if it were a finding.  :meth:`Predictor.attention_map` is built on ``attention``.
 """
 from __future__ import annotations
 
@@ -93,8 +119,9 @@ from .models.finetune import (ProteinBERTForSequenceClassification, ProteinBERTF
                               load_finetuned_head)
 
 OUTPUTS = ("global", "pooled", "residue", "go_probs", "go_topk", "residue_probs", "residue_tokens", "hidden_states",
-           "residue_llr", "residue_logp", "residue_entropy", "pll")
+           "residue_llr", "residue_logp", "residue_entropy", "pll", "attention", "attention_top")
 SCORE_OUTPUTS = ("residue_llr", "residue_logp", "residue_entropy", "pll")
+ATTENTION_OUTPUTS = ("attention", "attention_top")
 SCORE_STRATEGIES = ("wt_marginal", "pll_ratio")
 DEFAULT_OUTPUTS = ("global", "pooled", "go_topk")
 
@@ -112,9 +139,10 @@ def _task_request(o) -> Optional[Tuple[str, str]]:
     return None
 
 
-def _check_outputs(outputs: Iterable[str], heads: Optional[dict] = None) -> tuple:
+def _check_outputs(outputs: Iterable[str], heads: Optional[dict] = None, semantics: Optional[str] = None) -> tuple:
     """The requested names as a tuple: the built-in ``OUTPUTS`` and ``task:NAME`` / ``task_probs:NAME`` of the
-    registered ``heads``; anything else is ``unknown outputs``."""
+    registered ``heads``; anything else is ``unknown outputs``.  ``semantics``: the model's; the attention outputs
+    of a reference-semantics model raise (there is no attention map to show)."""
     if isinstance(outputs, str):
         outputs = (outputs,)
     outputs = tuple(outputs)
@@ -128,6 +156,12 @@ def _check_outputs(outputs: Iterable[str], heads: Optional[dict] = None) -> tupl
         if o not in OUTPUTS and r[0] == "task_probs" and _is_regression(heads[r[1]]):
             raise ValueError(f"{o}: {r[1]!r} is a regression head (n_classes == 1), it has values, not "
                              f"probabilities: request task:{r[1]}")
+    asked = [o for o in outputs if o in ATTENTION_OUTPUTS]
+    if asked and semantics is not None and semantics != "paper":
+        raise ValueError(f"{asked}: a semantics={semantics!r} model has no attention map: its attention softmax "
+                         f"runs over K identical query rows, so every weight is 1/K by construction and Wq / Wk "
+                         f"never influence the model (it computes the closed form); attention maps exist for "
+                         f"semantics='paper' models only")
     return outputs
 
 
@@ -250,14 +284,18 @@ class Predictor:
 
     # ------------------------------------------------------------------------
     def predict_batch(self, tokens: torch.Tensor, annotations: Optional[torch.Tensor] = None,
-                      outputs: Iterable[str] = DEFAULT_OUTPUTS, go_top_k: int = 10) -> Dict[str, torch.Tensor]:
+                      outputs: Iterable[str] = DEFAULT_OUTPUTS, go_top_k: int = 10,
+                      attention_top_k: int = 10) -> Dict[str, torch.Tensor]:
         """One encoder pass over ``tokens [B, L]`` int64 (and ``annotations [B, A]``, zeros when None):
         the requested outputs as tensors on the model's device, without any host synchronisation."""
-        outputs = _check_outputs(outputs, self.heads)
+        outputs = _check_outputs(outputs, self.heads, self.model.semantics)
         model = self.model
         A = model.config["num_annotations"]
         if ("go_topk" in outputs) and not 1 <= go_top_k <= A:
             raise ValueError(f"go_top_k={go_top_k}: expected 1 .. {A}")
+        if ("attention_top" in outputs) and not 1 <= attention_top_k <= tokens.shape[1]:
+            raise ValueError(f"attention_top_k={attention_top_k}: expected 1 .. {tokens.shape[1]} (the sequence "
+                             f"length)")
         tokens = tokens.to(self.device, non_blocking=True)
         ann = self._annotations(annotations, tokens.shape[0], self.device)
         # eval() for the model and the heads; every module's own flag is put back (a head holds the model as
@@ -269,8 +307,8 @@ class Predictor:
         try:
             with torch.no_grad():
                 if model.resolved_backend(self.device) == "hip":
-                    return self._predict_hip(tokens, ann, outputs, go_top_k)
-                return self._predict_torch(tokens, ann, outputs, go_top_k)
+                    return self._predict_hip(tokens, ann, outputs, go_top_k, attention_top_k)
+                return self._predict_torch(tokens, ann, outputs, go_top_k, attention_top_k)
         finally:
             for m, mode in modes:
                 m.training = mode
@@ -336,7 +374,28 @@ class Predictor:
         if "pll" in outputs:
             out["pll"], out["n_residues"] = pll, n_live
 
-    def _predict_hip(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
+    def _attention_outputs(self, out, outputs, hs, gs, g0, tokens, k, hip: bool) -> None:
+        """``attention`` / ``attention_top_*`` from this batch's tapped states: ``hs[i]`` / ``gs[i]`` the outputs
+        of block ``i``, ``g0`` the input layer's global output, so block ``i``'s query input is ``g0`` for
+        ``i = 0`` and ``gs[i - 1]`` otherwise."""
+        from .ops import attention_maps as am
+        from .ops import infer_heads as ih
+        atts = [blk.global_attention_layer for blk in self.model.proteinBERT_blocks]
+        Wqs, Wks = [a.Wq for a in atts], [a.Wk for a in atts]
+        if hip:
+            hs = [h.contiguous() for h in hs]
+        fn = am.attention_maps if hip and am.attention_supported(hs, Wks) else am.attention_maps_torch
+        att = fn(hs, [g0] + list(gs[:-1]), Wqs, Wks, tokens)                      # [B, blocks, H, L]
+        if "attention" in outputs:
+            out["attention"] = att
+        if "attention_top" in outputs:
+            B, nb, H, L = att.shape
+            rows = att.view(B * nb * H, L)
+            v, i = (ih.row_topk(rows, k) if hip and att.is_cuda and ih.topk_supported(L, k)
+                    else stable_topk_torch(rows, k))
+            out["attention_top_values"], out["attention_top_indices"] = v.view(B, nb, H, k), i.view(B, nb, H, k)
+
+    def _predict_hip(self, tokens, ann, outputs, k, att_k=10) -> Dict[str, torch.Tensor]:
         from .ops import infer_heads as ih
         from .ops.fused_model import fused_encode
         model = self.model
@@ -348,7 +407,9 @@ class Predictor:
         gs_all: List[torch.Tensor] = []
         want_hidden = "hidden_states" in outputs
         req = self._task_requests(outputs)
-        want_all = self._needs_all(req)
+        want_att = any(o in outputs for o in ATTENTION_OUTPUTS)
+        want_all = self._needs_all(req) or want_att
+        g_first: List[torch.Tensor] = []
 
         def tap(i, h_i, g_i):
             if want_all:
@@ -359,7 +420,8 @@ class Predictor:
                 hidden_p.append(ih.masked_mean_pool(h_i.contiguous(), tokens))  # one pool launch per block
 
         h, g, g_bf = fused_encode(model, tokens, ann, return_bf16=True,
-                                  tap=tap if (want_hidden or want_all) else None)
+                                  tap=tap if (want_hidden or want_all) else None,
+                                  tap_input=g_first.append if want_att else None)
         h = h.contiguous()
         out: Dict[str, torch.Tensor] = {}
         if "global" in outputs:
@@ -387,9 +449,11 @@ class Predictor:
             out["hidden_pooled"] = torch.stack(hidden_p, dim=1)
         self._score_outputs(out, outputs, ih.local_scores, h, tokens)
         self._task_outputs(out, req, tokens, h, g, hs_all, gs_all, hip=True)
+        if want_att:
+            self._attention_outputs(out, outputs, hs_all, gs_all, g_first[0], tokens, att_k, hip=True)
         return out
 
-    def _predict_torch(self, tokens, ann, outputs, k) -> Dict[str, torch.Tensor]:
+    def _predict_torch(self, tokens, ann, outputs, k, att_k=10) -> Dict[str, torch.Tensor]:
         model = self.model
         hidden_g: List[torch.Tensor] = []
         hidden_p: List[torch.Tensor] = []
@@ -398,7 +462,9 @@ class Predictor:
         gs_all: List[torch.Tensor] = []
         want_hidden = "hidden_states" in outputs
         req = self._task_requests(outputs)
-        want_all = self._needs_all(req)
+        want_att = any(o in outputs for o in ATTENTION_OUTPUTS)
+        want_all = self._needs_all(req) or want_att
+        g_first: List[torch.Tensor] = []
 
         def tap(i, h_i, g_i):
             if want_all:
@@ -408,7 +474,8 @@ class Predictor:
                 hidden_g.append(g_i.float())
                 hidden_p.append(masked_mean_torch(h_i, tokens))
 
-        h, g = model.encode_torch(tokens, ann, tap=tap if (want_hidden or want_all) else None)
+        h, g = model.encode_torch(tokens, ann, tap=tap if (want_hidden or want_all) else None,
+                                  tap_input=g_first.append if want_att else None)
         out: Dict[str, torch.Tensor] = {}
         if "global" in outputs:
             out["global"] = g.float()
@@ -435,17 +502,20 @@ class Predictor:
         from .ops.infer_heads import local_scores_torch
         self._score_outputs(out, outputs, local_scores_torch, h, tokens)
         self._task_outputs(out, req, tokens, h, g, hs_all, gs_all, hip=False)
+        if want_att:
+            self._attention_outputs(out, outputs, hs_all, gs_all, g_first[0], tokens, att_k, hip=False)
         return out
 
     # ------------------------------------------------------------------------
     def predict(self, sequences: Union[Sequence[str], torch.Tensor], annotations: Optional[torch.Tensor] = None,
                 outputs: Iterable[str] = DEFAULT_OUTPUTS, go_top_k: int = 10,
-                truncate: bool = False) -> Dict[str, torch.Tensor]:
+                truncate: bool = False, attention_top_k: int = 10) -> Dict[str, torch.Tensor]:
         """Predictions for ``sequences`` (a list of strings, tokenised by :meth:`tokenize`; or an int64 token
         tensor ``[N, L]``, taken as it is) in batches of ``batch_size``: CPU tensors in input order.  No host
         synchronisation per batch: every batch's outputs are copied, without blocking, into host tensors
-        allocated once (pinned when the model is on a GPU), and the device is synchronised once at the end."""
-        outputs = _check_outputs(outputs, self.heads)
+        allocated once (pinned when the model is on a GPU), and the device is synchronised once at the end.
+        ``go_top_k`` / ``attention_top_k``: the ``k`` of the ``go_topk`` / ``attention_top`` outputs."""
+        outputs = _check_outputs(outputs, self.heads, self.model.semantics)
         tokens = sequences if isinstance(sequences, torch.Tensor) else self.tokenize(list(sequences), truncate)
         if tokens.dim() != 2 or tokens.dtype != torch.int64:
             raise ValueError("token input must be an int64 [N, L] tensor")
@@ -457,7 +527,7 @@ class Predictor:
         for s in range(0, N, self.batch_size):
             e = min(N, s + self.batch_size)
             out = self.predict_batch(tokens[s:e], None if annotations is None else annotations[s:e], outputs,
-                                     go_top_k)
+                                     go_top_k, attention_top_k)
             for name, t in out.items():
                 if name not in host:
                     host[name] = torch.empty((N,) + tuple(t.shape[1:]), dtype=t.dtype, pin_memory=cuda)
@@ -526,3 +596,14 @@ class Predictor:
         return {"llr": out["residue_llr"][0, rows].index_select(-1, cols).cpu(),
                 "logp": out["residue_logp"][0, rows].cpu(), "entropy": out["residue_entropy"][0, rows].cpu(),
                 "pll": float(out["pll"][0]), "letters": ALL_AMINO_ACIDS}
+
+    def attention_map(self, sequence: str, truncate: bool = False) -> dict:
+        """Where the model looks on one sequence, from a single encoder pass (paper semantics only; a
+        reference-semantics model raises ``ValueError``, see the module docstring): ``attention [blocks, H,
+        n + 2]`` (the weights of every block and head over the ``<sos>``, residue and ``<eos>`` columns, the
+        ``<pad>`` columns trimmed: every row sums to 1), ``per_block [blocks, n + 2]`` (the sum over the heads)
+        and ``letters`` (the ``n + 2`` column labels: ``"<sos>"``, the residues, ``"<eos>"``), as CPU tensors."""
+        _check_outputs(("attention",), self.heads, self.model.semantics)        # before the sequence is touched
+        tokens, seq = self._wild_type(sequence, truncate)
+        att = self.predict_batch(tokens, outputs=("attention",))["attention"][0, :, :, :len(seq) + 2].cpu()
+        return {"attention": att, "per_block": att.sum(dim=1), "letters": ["<sos>"] + list(seq) + ["<eos>"]}

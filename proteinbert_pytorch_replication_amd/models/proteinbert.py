@@ -357,14 +357,19 @@ class ProteinBERT(nn.Module):
 
     def encode_torch(self, tokens: torch.Tensor, annotations: torch.Tensor,
                      compute_dtype: Optional[torch.dtype] = None,
-                     faithful_attention: bool = False, tap=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``tap``: called as ``tap(i, h_i, g_i)`` after block ``i`` with that block's outputs."""
+                     faithful_attention: bool = False, tap=None,
+                     tap_input=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``tap``: called as ``tap(i, h_i, g_i)`` after block ``i`` with that block's outputs.  ``tap_input``:
+        called once as ``tap_input(g0)`` with the input layer's global output, before the first block (block
+        ``i``'s attention query then comes from ``g0`` for ``i = 0``, else from the ``g`` of tap ``i - 1``)."""
         self.check_length(tokens.shape[1])
         dt = compute_dtype or torch.float32
         h = self.local_embedding.weight.to(dt)[tokens]                       # [B,L,C]
         lin = self.global_linear_layer[0]
         g = _gelu(F.linear(annotations.to(dt), lin.weight.to(dt), lin.bias.to(dt))).float()
         mask = tokens != 0 if self.semantics == "paper" else None
+        if tap_input is not None:
+            tap_input(g)
         for i, blk in enumerate(self.proteinBERT_blocks):
             h, g = blk.forward_torch(h, g, mask, faithful_attention)
             if tap is not None:

@@ -48,16 +48,22 @@ def _check(model) -> None:
 
 
 def fused_encode(model, tokens: torch.Tensor, annotations: torch.Tensor,
-                 return_bf16: bool = False, cp=None, tap=None):
+                 return_bf16: bool = False, cp=None, tap=None, tap_input=None):
     """Encoder on the HIP path: returns ``h [B, L, 128]`` (bf16) and ``g [B, G]`` (fp32).
 
     ``tap``: called as ``tap(i, h_i, g_i)`` after block ``i`` with that block's outputs (the per-block
     representations of :mod:`..inference`); ``None`` changes nothing.
 
+    ``tap_input``: called once as ``tap_input(g0)`` with the input layer's global output, before the first
+    block: with ``tap`` it gives every block's query input (``g0`` for block 0, the ``g`` of tap ``i - 1``
+    otherwise; :mod:`.attention_maps`); ``None`` changes nothing.  Not available with ``cp``.
+
     ``cp`` (:class:`..parallel.cp_fused.CPShard`): ``tokens`` is this rank's slice of the sequence;
     the local track runs on the slice (halo rows and LayerNorm statistics exchanged inside the block),
     the global track is replicated from the group-wide attention-pool sum."""
     _check(model)
+    if cp is not None and tap_input is not None:
+        raise NotImplementedError("fused_encode: tap_input is not available on a context-parallel shard")
     if cp is None:
         model.check_length(tokens.shape[1])   # the kernels index the [L, C] LayerNorm affine by position
     else:
@@ -69,6 +75,8 @@ def fused_encode(model, tokens: torch.Tensor, annotations: torch.Tensor,
     gl0 = blocks[0].global_to_local_linear_layer[0]
     # g0 and block 0's global->local vector; every GlobalBlockFn then produces the next block's gb
     g, g_bf, gb = InputLayerFn.apply(annotations, lin.weight, lin.bias, gl0.weight, gl0.bias)
+    if tap_input is not None:
+        tap_input(g)
     paper = model.semantics == "paper"
     emb_w = model.local_embedding.weight
     tok_c = tokens.contiguous()
